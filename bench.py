@@ -7,12 +7,16 @@ inputs resident in HBM before the timed region.  Metric: feature-depth associati
 wall time (every submitted feature counts).
 
 stdout carries exactly ONE line: a compact JSON object (< 4 KB; tests/test_bench_gpu.py asserts <= 8192 bytes) with the
-contract's keys, `verified` (every frame of the timed batch re-computed by the CPU oracle; exit 1 if not), a physical
-`roofline` and `cpu_baseline`.  Everything else - per-kernel rooflines, per-loop times, the verification report and the
-SECONDARY LEGS (plane-estimated schedule, PCIe-inclusive latency / streaming, BASELINE configs 2 at k = 7, 3 and 5; run by
-`bench_support/run_legs.py` in a child process with a timeout, so a failing leg cannot take the headline line down) - goes
-to the detail file (`--detail`, default gpurun_out/bench_detail.json); the compact line names it and carries the legs'
-verified flags.  The exit code follows the HEADLINE's `verified` only; leg failures are reported in `legs`.
+contract's keys.  A plain run does only what that line's headline needs: it sets up, warms up, times ONE loop of exactly
+`--steps` steps, writes the outputs of the last step if `--dump-outputs DIR` is given, and prints the line (`verified`,
+`roofline` and `cpu_baseline` null, `full` false).  `--full` adds everything else as before: the timed loop repeated
+(`--repeats`, `--min-timed-seconds`; value = median loop), `verified` (every frame of the timed batch re-computed by the CPU
+oracle; exit 1 if not), a physical `roofline` and `cpu_baseline` on the line, and in the detail file (`--detail`) the
+per-kernel rooflines, per-loop times, the verification report and the SECONDARY LEGS (plane-estimated schedule,
+PCIe-inclusive latency / streaming, BASELINE configs 2 at k = 7, 3 and 5; run by `bench_support/run_legs.py` in a child
+process with a timeout, so a failing leg cannot take the headline line down); the compact line names the detail file and
+carries the legs' verified flags.  The exit code follows the HEADLINE's `verified` only; leg failures are reported in
+`legs`.
 
 Multi-GPU: one process per GPU, each rank owns its own sequence (weak scaling); the only collective is the RCCL
 broadcast of the calibration block.  `python bench.py --gpus N` starts the N ranks itself (torch.distributed.run as a
@@ -47,8 +51,21 @@ def log(*a):
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200, help="timed steps per loop (0.15 s of GPU time at the default)")
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=200,
+                    help="timed steps (one loop of exactly this many; with --full, per loop of --repeats loops)")
+    ap.add_argument("--warmup", type=int, default=5,
+                    help="untimed steps before the timed ones (without --full: repeated until --warmup-seconds have passed)")
+    ap.add_argument("--warmup-seconds", type=float, default=0.5,
+                    help="least wall time of the warm-up without --full, so that the GPU clocks have settled")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: --repeats loops, per-kernel timing and rooflines, the check of the "
+                         "timed batch against the CPU oracle, cpu_baseline, the secondary legs and the detail file. Without "
+                         "it a run sets up, warms up, times --steps steps and prints the line; --repeats, --min-timed-seconds, "
+                         "--cpu-seconds, --verify-slots, --no-exclusive, --no-kernel-timing, --timing-every, --detail, --legs "
+                         "and the sizes of the legs act only with it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed (depth, result_type: float64 / float32 "
+                         ".npy, at most 64 MB; a fixed seeded sample of frames beyond that) into DIR")
     ap.add_argument("--frames-per-step", type=int, default=1024, help="resident frames processed per step")
     ap.add_argument("--slots", type=int, default=0,
                     help="frame slots of the context (0 = frames-per-step); a step runs frames-per-step/slots launch sets")
@@ -75,10 +92,10 @@ def parse_args():
                     help="frames of the timed batch checked against the oracle: -1 (default) = EVERY frame of every "
                          "context's output set; n > 0 = n frames spread over the output sets; 0 = no check")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed loop of --steps steps runs at least this many times back to back; value / "
+                    help="--full: the timed loop of --steps steps runs at least this many times back to back; value / "
                          "ms_per_step are the median loop, ms_per_step_min / _max the spread")
     ap.add_argument("--min-timed-seconds", type=float, default=0.5,
-                    help="the timed loop is repeated beyond --repeats until this much time has been timed in all (at "
+                    help="--full: the timed loop is repeated beyond --repeats until this much time has been timed in all (at "
                          "most 64 loops): a 20-step loop is 15 ms, less than the GPU clocks take to settle")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--timing-every", type=int, default=4,
@@ -282,6 +299,73 @@ def brief(detail):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ headline, outputs
+def headline(args, world, B, F, S, N, value, elapsed, loops):
+    """The keys of the result line that every run prints (the median loop of --steps steps, max over ranks); a plain run
+    leaves the checks and the figures that only --full measures at None."""
+    return {
+        "metric": "feature-depth associations/sec",
+        "value": value,
+        "unit": "feature-depth associations/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "ms_per_frame": 1e3 * elapsed / args.steps / (B * world),  # whole job: all ranks' frames
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "full": bool(args.full),
+        "verified": None,
+        "config": {
+            "workload": f"BASELINE config 2: 64x2048 cloud x {F} features/frame, C0 parameters, {B} HBM-resident frames/step/GPU",
+            "frames_per_step": B, "frame_slots_per_launch": S, "features_per_frame": F, "points_per_frame": N,
+            "contexts": args.contexts, "sequences": world, "parallelism": f"sequence-per-gpu x{world}",
+        },
+        "roofline": None,
+        "cpu_baseline": None,
+        "ms_per_step_min": 1e3 * min(loops) / args.steps,
+        "ms_per_step_max": 1e3 * max(loops) / args.steps,
+        "timed_loops": len(loops),
+    }
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir, rank, world):
+    """What the last timed step handed back - the depth and result type of every feature of every frame of the step, as the
+    caller's output buffers hold them - as out_dir/depth.npy (float64) and out_dir/result_type.npy (float32, exact for
+    the small integer codes), each (frames, features).  Beyond 64 MB in all (shared by the ranks) a fixed, seeded sample of
+    frames (and of features, should one frame exceed the share) is written, its indices in frames.npy / features.npy.
+    Rank r > 0 writes its own sequence's arrays with the suffix _rank<r>."""
+    o = (res.k - 1) % len(res.batches) if res.whole else 0   # the output set the last step wrote
+    res.sync()
+    depth = res.out_depth[o].cpu().numpy().astype(np.float64, copy=False)
+    rtype = res.out_type[o].cpu().numpy().astype(np.float32)
+    arrays = {"depth": depth, "result_type": rtype}
+    B, F = depth.shape
+    budget = DUMP_BYTES // max(1, world)
+    per_value = depth.itemsize + rtype.itemsize
+    if B * F * per_value > budget:
+        rng = np.random.default_rng(20240601)
+        cols = np.arange(F)
+        if F * per_value > budget:
+            cols = np.sort(rng.choice(F, budget // per_value, replace=False))
+        rows = np.sort(rng.choice(B, min(B, max(1, budget // (len(cols) * per_value))), replace=False))
+        arrays = {k: v[np.ix_(rows, cols)] for k, v in arrays.items()}
+        arrays["frames"] = rows.astype(np.float64)
+        if len(cols) < F:
+            arrays["features"] = cols.astype(np.float64)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for k, v in arrays.items():
+        np.save(out_dir / f"{k}{suffix}.npy", np.ascontiguousarray(v))
+    log(f"bench.py: outputs of the last timed step in {out_dir} ({', '.join(arrays)})")
+
+
 # ------------------------------------------------------------------------------------------------ worker
 def main():
     args = parse_args()
@@ -372,13 +456,30 @@ def main():
         if world > 1:
             dist.barrier()
 
-    timing = not args.no_kernel_timing
-    loops, kt = timed_resident(res, args.steps, args.warmup, timing, args.timing_every, barrier, repeats=args.repeats,
+    full = args.full
+    timing = full and not args.no_kernel_timing
+    # without --full: one loop of exactly --steps steps behind a warm-up of at least --warmup-seconds
+    loops, kt = timed_resident(res, args.steps, args.warmup, timing, args.timing_every, barrier,
+                               repeats=args.repeats if full else 1,
                                reduce_max=lambda x: sharding.max_over_ranks(x, device=coll_dev),
-                               min_timed_s=args.min_timed_seconds)
+                               min_timed_s=args.min_timed_seconds if full else 0.0,
+                               min_warmup_s=0.0 if full else args.warmup_seconds)
+    if args.dump_outputs:
+        dump_outputs(res, Path(args.dump_outputs), rank, world)
     elapsed = float(np.median(loops))  # every loop: exactly --steps steps, max over ranks
     elapsed_local = float(np.median(res.local_loops)) if getattr(res, "local_loops", None) else elapsed
     units = sharding.sum_over_ranks(float(B * F * args.steps), device=coll_dev)
+    value = units / elapsed
+    line = headline(args, world, B, F, S, N, value, elapsed, loops)
+    if not full:
+        res.close()
+        if rank == 0:
+            if world > 1:
+                line["distributed"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size()}
+            os.write(line_fd, (json.dumps(line) + "\n").encode())
+        if world > 1:
+            dist.destroy_process_group()
+        sys.exit(0)
 
     # ---- the timed batch against the oracle (every rank checks its own sequence) ---------------------------
     verified, vrep = res.verify(args.verify_slots) if args.verify_slots != 0 else (None, {})
@@ -461,37 +562,15 @@ def main():
     del res
     torch.cuda.empty_cache()
 
-    value = units / elapsed
-    line = {
-        "metric": "feature-depth associations/sec",
-        "value": value,
-        "unit": "feature-depth associations/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "ms_per_frame": 1e3 * elapsed / args.steps / (B * world),  # whole job: all ranks' frames
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
+    line.update({
         "verified": verified,
-        "config": {
-            "workload": f"BASELINE config 2: 64x2048 cloud x {F} features/frame, C0 parameters, {B} HBM-resident frames/step/GPU",
-            "frames_per_step": B, "frame_slots_per_launch": S, "features_per_frame": F, "points_per_frame": N,
-            "contexts": args.contexts, "sequences": world, "parallelism": f"sequence-per-gpu x{world}",
-        },
         "roofline": roofline,
         "cpu_baseline": ({k: cpu[k] for k in ("value", "unit", "cores", "kind", "sample", "ms_per_frame") if k in cpu}
                          if cpu and "error" not in cpu else cpu),
-        "ms_per_step_min": 1e3 * min(loops) / args.steps,
-        "ms_per_step_max": 1e3 * max(loops) / args.steps,
-        "timed_loops": len(loops),
         "frames_checked": vrep.get("frames_checked"),
         "max_abs_depth_diff_m": vrep.get("max_abs_depth_diff_m"),
         "success_fraction": float((type_hist[1] + type_hist[16]) / max(1, type_hist.sum())),
-    }
+    })
     if distributed:
         line["distributed"] = {k: distributed[k] for k in ("backend", "world_size", "gpus_distinct", "ranks_verified")}
         if streaming_ranks and "frames_per_s" in streaming_ranks:

@@ -259,15 +259,22 @@ def kernel_times(ests):
 
 
 def timed_resident(res, steps, warmup, timing, timing_every, barrier=lambda: None, estimated=False, repeats=1,
-                   reduce_max=lambda x: x, min_timed_s=0.0):
+                   reduce_max=lambda x: x, min_timed_s=0.0, min_warmup_s=0.0):
     """At least `repeats` timed loops of `steps` steps each (more until `min_timed_s` seconds have been timed, at most
-    64), every loop bracketed by barrier + synchronize on both sides.  Returns (per-loop elapsed seconds, each the max
-    over ranks; kernel times averaged over the sampled steps of all loops)."""
+    64), every loop bracketed by barrier + synchronize on both sides.  The warm-up runs `warmup` steps, and more until
+    `min_warmup_s` seconds have passed (every rank runs the same number: the count follows the max over ranks).  Returns
+    (per-loop elapsed seconds, each the max over ranks; kernel times averaged over the sampled steps of all loops)."""
     import torch
     step = res.run_step_estimated if estimated else res.run_step
     for _ in range(warmup):
         step()
     res.sync()
+    if min_warmup_s > 0:
+        t0 = time.perf_counter()
+        while reduce_max(time.perf_counter() - t0) < min_warmup_s:
+            for _ in range(max(1, warmup)):
+                step()
+            res.sync()
     res.poison()
     if timing:
         for e in res.ests:

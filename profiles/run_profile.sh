@@ -7,14 +7,14 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-COMMON="--cpu-seconds 0 --legs none"
+COMMON="--full --cpu-seconds 0 --legs none"
 LEGS=$REPO/bench_support/run_legs.py
 ARGS="--steps 200 --warmup 5 --repeats 1 $COMMON"
 # (second argument "latency": only the one-frame legs are re-run, the rest of gpurun_out/prof_<tag>/ is kept)
 ONLY=${2:-all}
 if [ "$ONLY" = all ]; then
 # the driver's own command, un-traced: the line of record and its detail file
-(cd $REPO && python3 bench.py --gpus 1 --steps 20 --warmup 5 --detail $OUT/bench_default_detail.json > $OUT/bench_default.json 2> $OUT/bench_default.log)
+(cd $REPO && python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --detail $OUT/bench_default_detail.json > $OUT/bench_default.json 2> $OUT/bench_default.log)
 # the bench default: two contexts alternating (a projection beside the other context's feature kernels)
 # (only launches of the timed schedule in this trace: no plane-estimated leg, no kernels-alone pass)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $REPO/bench.py $ARGS --no-exclusive --detail $OUT/bench_trace.json > $OUT/bench_trace_line.json 2> $OUT/trace.log

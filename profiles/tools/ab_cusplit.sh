@@ -2,7 +2,7 @@
 # usage: ab_cusplit.sh ROUNDS  - the bench default schedule against CU-split schedules on ONE box: the pair's projection
 # stream confined to N CUs, classification + feature kernels to the other 256 - N (test build, MLD_CU_SPLIT; LAB.md).
 ROUNDS=${1:-2}
-COMMON="--steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-estimated --verify-slots 16"
+COMMON="--full --steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-estimated --verify-slots 16"
 AB="MLD_HIP_LIBRARY=$PWD/mono_lidar_depth_amd/lib/libmld_hip_ab.so"
 run() {  # label, env, extra bench args
   echo -n "$1: "

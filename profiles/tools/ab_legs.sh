@@ -2,7 +2,7 @@
 # usage: ab_legs.sh ROUNDS lib ...  - per library variant on ONE box: the config-2 default schedule, config 2 at k = 7
 #   (--only-config 2), config 3 with the features around the returns (--only-config 3 --leg near).
 ROUNDS=$1; shift
-C2="--steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-estimated --verify-slots 32"
+C2="--full --steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-estimated --verify-slots 32"
 for round in $(seq 1 $ROUNDS); do
 for lib in "$@"; do
   case "$lib" in

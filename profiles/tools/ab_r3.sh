@@ -2,7 +2,7 @@
 # usage: ab_r3.sh ROUNDS "lib[:bench args]" ...   - default bench.py schedule per variant on ONE box, ROUNDS times
 # (lib = name of profiles/tools/libs/<name>.so, or "-" for the in-tree library)
 ROUNDS=$1; shift
-COMMON="--steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-estimated"
+COMMON="--full --steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-estimated"
 for round in $(seq 1 $ROUNDS); do
 for v in "$@"; do
   lib=${v%%:*}; extra=""; [[ "$v" == *:* ]] && extra=${v#*:}

@@ -2,7 +2,7 @@
 # usage: ab_r4.sh ROUNDS "lib[@ENV=V,ENV2=V][:bench args]" ...  - the bench default schedule per variant on ONE box.
 #   lib = "-" (in-tree product library), "ab" (in-tree test build), or NAME of profiles/tools/libs/NAME.so
 ROUNDS=$1; shift
-COMMON="--steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-estimated --verify-slots 32"
+COMMON="--full --steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-estimated --verify-slots 32"
 for round in $(seq 1 $ROUNDS); do
 for v in "$@"; do
   spec=${v%%:*}; extra=""; [[ "$v" == *:* ]] && extra=${v#*:}

@@ -3,7 +3,7 @@
 #   per call and the batched legs) and the config-2 default schedule.  lib = "-" (in-tree product library) or NAME of
 #   profiles/tools/libs/NAME.so (mkvariant.sh).  MLD_AB_C2=0 skips the config-2 line.
 ROUNDS=$1; shift
-C2="--steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-estimated --verify-slots 32"
+C2="--full --steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-estimated --verify-slots 32"
 for round in $(seq 1 $ROUNDS); do
 for lib in "$@"; do
   case "$lib" in

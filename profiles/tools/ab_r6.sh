@@ -7,7 +7,7 @@
 # lib = "-" (in-tree product library) or NAME of profiles/tools/libs/NAME.so (mkvariant.sh).  MLD_AB_LEGS="c2 2k1 3n 5b256" selects.
 ROUNDS=$1; shift
 LEGS=${MLD_AB_LEGS:-"c2 2k1 3n 5b256"}
-C2="--steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --legs none --verify-slots 32"
+C2="--full --steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --legs none --verify-slots 32"
 for round in $(seq 1 $ROUNDS); do
 for lib in "$@"; do
   case "$lib" in

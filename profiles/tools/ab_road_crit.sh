@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: ab_road_crit.sh lib ...  - per library variant (NAME.so = product build, NAME_ab.so = test build) on ONE box: the
 #   config-2 default step and the 5000-configuration parity sweep on the lane-per-feature route (LAB.md 5.33)
-C2="--steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-estimated --no-exclusive"
+C2="--full --steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-estimated --no-exclusive"
 for lib in "$@"; do
   echo -n "$lib c2: "
   MLD_HIP_LIBRARY=$PWD/profiles/tools/libs/$lib.so python bench.py $C2 2>/dev/null | python profiles/tools/show_step.py

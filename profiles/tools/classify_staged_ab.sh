@@ -2,7 +2,7 @@
 # k_classify with the bitmap staged in LDS (68 KB per block: cannot start on a CU whose LDS the other context's feature
 # wavefronts hold) against reading it in place (4 KB): the config-2 default schedule and the k = 7 leg, one box.
 AB="MLD_HIP_LIBRARY=$PWD/mono_lidar_depth_amd/lib/libmld_hip_ab.so"
-C2="--steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-estimated --verify-slots 32"
+C2="--full --steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-estimated --verify-slots 32"
 for round in 1 2; do
 for st in 1 0; do
   echo -n "staged=$st r$round c2: "

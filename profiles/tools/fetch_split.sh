@@ -4,7 +4,7 @@
 # without the point gathers, without both (wrong results; libs built with mkvariant.sh NAME -DMLD_AB_SWITCHES -DMLD_DIAG_NO_KEYS ...)
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
-A="--contexts 1 --steps 3 --warmup 1 --repeats 1 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-kernel-timing --no-estimated --verify-slots 0"
+A="--full --contexts 1 --steps 3 --warmup 1 --repeats 1 --cpu-seconds 0 --latency-frames 0 --streaming-batches 0 --config-frames 0 --no-kernel-timing --no-estimated --verify-slots 0"
 for lib in cur nokeys nopoints nogathers; do
   OUT=$REPO/gpurun_out/fsplit_$lib; rm -rf $OUT; mkdir -p $OUT
   export MLD_HIP_LIBRARY=$REPO/profiles/tools/libs/$lib.so

@@ -3,7 +3,7 @@
 # the shipped library against the test build without the helper thread (MLD_FRAME_HELPER=0) and with MLD_FRAME_COPY=1
 # (results through device memory + a D2H copy), same box
 ROUNDS=${1:-2}
-COMMON="--steps 4 --warmup 1 --repeats 1 --min-timed-seconds 0 --no-estimated --config-frames 0 --streaming-batches 0 --cpu-seconds 0 --frames-per-step 64 --verify-slots 4 --no-exclusive"
+COMMON="--full --steps 4 --warmup 1 --repeats 1 --min-timed-seconds 0 --no-estimated --config-frames 0 --streaming-batches 0 --cpu-seconds 0 --frames-per-step 64 --verify-slots 4 --no-exclusive"
 for r in $(seq 1 $ROUNDS); do
 for v in product nohelper copy; do
   case $v in

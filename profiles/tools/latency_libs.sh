@@ -2,7 +2,7 @@
 # usage: latency_libs.sh ROUNDS lib ...  - the one-frame latency legs of bench.py for library variants (profiles/tools/libs/NAME.so;
 # "-" = the in-tree product library) on one box: median / p99 of the call and the GPU phases of the instrumented pass
 ROUNDS=$1; shift
-COMMON="--steps 4 --warmup 1 --repeats 1 --min-timed-seconds 0 --no-estimated --config-frames 0 --streaming-batches 0 --cpu-seconds 0 --frames-per-step 64 --verify-slots 4 --no-exclusive --latency-frames 300"
+COMMON="--full --steps 4 --warmup 1 --repeats 1 --min-timed-seconds 0 --no-estimated --config-frames 0 --streaming-batches 0 --cpu-seconds 0 --frames-per-step 64 --verify-slots 4 --no-exclusive --latency-frames 300"
 for r in $(seq 1 $ROUNDS); do
 for lib in "$@"; do
   case "$lib" in

@@ -10,8 +10,9 @@ import json,sys
 d=json.loads(sys.stdin.read()); e=d['plane_estimated']
 print('chunks ${MLD_PROJ_CHUNKS:-1} [$1]', 'estimated step', round(e['ms_per_step'],4), {k:round(v*1e3,1) for k,v in e['kernels_ms_per_launch'].items()}, 'frames/launch', e['frame_slots_per_launch'], e['verified'])"
 }
+T=$(mktemp -d)   # stderr of the headline runs
 head() {
-python bench.py --steps 100 --warmup 5 --repeats 2 --cpu-seconds 0 --legs none $1 2>gpurun_out/est.err | tail -1 | python -c "
+python bench.py --full --steps 100 --warmup 5 --repeats 2 --cpu-seconds 0 --legs none $1 2>$T/est.err | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('chunks ${MLD_PROJ_CHUNKS:-1} headline [$1]', round(d['ms_per_step'],4), d['roofline']['kernels_ms'], d['verified'])"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Wavefronts of k_feature_fused per CU in the shared-GPU mode of the two-context schedule (mld_set_shared_gpu bits 8..15;
 # 1 = the default, 8): usage: shared_mode_sweep.sh [n ...]   (default: 8 10 12 14 16)
-C2="--steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --legs none --verify-slots 32 --no-exclusive"
+C2="--full --steps 60 --warmup 5 --repeats 3 --cpu-seconds 0 --legs none --verify-slots 32 --no-exclusive"
 for n in ${@:-8 10 12 14 16}; do
   sm=$((1 + 256 * n))
   echo -n "feature wavefronts per CU $n (shared-mode $sm): "

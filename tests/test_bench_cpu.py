@@ -6,6 +6,8 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
+
 ROOT = Path(__file__).resolve().parent.parent
 
 
@@ -62,3 +64,27 @@ def test_roofline_rule_is_the_longest_average_launch():
         assert abs(compact["frac"] - nbytes / (compact["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS) < 1e-12
         assert compact["frac"] <= 1.0 and "formula_frac" not in compact and len(json.dumps(compact)) < 2048
         assert set(detail["kernels"]) == set(kt) and detail["kernels"]["k_project_scatter"]["formula_frac"] > 0
+
+
+def test_dump_outputs_writes_the_last_output_set_and_samples_beyond_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs without a GPU: the output set of the context that ran the last step, float64 depths and float32
+    result types; past the byte budget a seeded sample of frames, the same from call to call, with its indices."""
+    import types
+    import torch
+    b = _bench()
+    B, F = 8, 50
+    depth = [torch.full((B, F), float(c), dtype=torch.float64) for c in (1, 2)]
+    rtype = [torch.full((B, F), c, dtype=torch.int32) for c in (1, 16)]
+    res = types.SimpleNamespace(k=8, whole=True, batches=[0, 1], out_depth=depth, out_type=rtype, sync=lambda: None)
+    b.dump_outputs(res, tmp_path / "all", 0, 1)
+    d, t = np.load(tmp_path / "all" / "depth.npy"), np.load(tmp_path / "all" / "result_type.npy")
+    assert d.dtype == np.float64 and t.dtype == np.float32 and d.shape == t.shape == (B, F)
+    assert (d == 2.0).all() and (t == 16.0).all()   # (8 steps dealt to two contexts in turn: the last ran on the second)
+    assert not (tmp_path / "all" / "frames.npy").exists()
+    monkeypatch.setattr(b, "DUMP_BYTES", 3 * F * 12)
+    for sub in ("s1", "s2"):
+        b.dump_outputs(res, tmp_path / sub, 0, 1)
+    f1, f2 = (np.load(tmp_path / s / "frames.npy") for s in ("s1", "s2"))
+    assert f1.dtype == np.float64 and len(f1) == 3 and np.array_equal(f1, f2) and (np.diff(f1) > 0).all()
+    assert np.load(tmp_path / "s1" / "depth.npy").shape == (3, F)
+    assert sum((tmp_path / "s1").joinpath(n).stat().st_size for n in ("depth.npy", "result_type.npy")) <= 3 * F * 12 + 512

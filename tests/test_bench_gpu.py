@@ -7,13 +7,15 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 pytestmark = pytest.mark.gpu
 
-SMALL = ["--steps", "2", "--warmup", "1", "--repeats", "2", "--frames-per-step", "32", "--unique-frames", "4", "--cpu-seconds", "0",
-         "--legs", "none"]
+SMALL = ["--full", "--steps", "2", "--warmup", "1", "--repeats", "2", "--frames-per-step", "32", "--unique-frames", "4",
+         "--cpu-seconds", "0", "--legs", "none"]
+PLAIN = ["--steps", "3", "--warmup", "1", "--frames-per-step", "32", "--unique-frames", "4"]
 REQUIRED = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "verified", "config", "roofline", "cpu_baseline")
 
@@ -147,7 +149,7 @@ def test_bench_gpus_8_over_gloo_every_rank_its_own_sequence(tmp_path):
     """BASELINE config 4's layout at full rank count where only one GPU is visible: eight ranks (sequences 0 ... 7), one
     calibration broadcast, no data-path collective, every rank verifies and streams its own sequence.  (On an 8-GPU node
     the same command without the hook runs over RCCL: `backend: nccl`, `gpus_distinct: 8`.)"""
-    tiny = ["--steps", "2", "--warmup", "1", "--repeats", "1", "--min-timed-seconds", "0", "--frames-per-step", "8",
+    tiny = ["--full", "--steps", "2", "--warmup", "1", "--repeats", "1", "--min-timed-seconds", "0", "--frames-per-step", "8",
             "--unique-frames", "2", "--features", "500", "--cpu-seconds", "0", "--streaming-batches", "2",
             "--streaming-frames", "2", "--no-exclusive"]
     out = _run(["--gpus", "8"] + tiny, {"MLD_BENCH_BACKEND": "gloo"}, tmp=tmp_path)
@@ -159,6 +161,39 @@ def test_bench_gpus_8_over_gloo_every_rank_its_own_sequence(tmp_path):
     st = out["_detail"]["streaming"]
     assert st["ranks"] == 8 and st["frames"] == 4 and st["frames_per_s"] > 0
     assert out["value"] > 0 and out["scaling"] == "weak" and out["config"]["parallelism"] == "sequence-per-gpu x8"
+
+
+def test_bench_plain_run_times_exactly_the_steps_and_checks_nothing_else():
+    """Without --full: one loop of exactly --steps steps, the headline keys, nothing measured or checked beyond them."""
+    out = _run(PLAIN)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in out, k
+    assert out["metric"] == "feature-depth associations/sec" and out["unit"] == "feature-depth associations/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f64" and out["full"] is False
+    assert out["steps"] == 3 and out["timed_loops"] == 1 and out["ms_per_step_min"] == out["ms_per_step"] == out["ms_per_step_max"]
+    assert out["value"] > 0 and abs(out["value"] - 32 * 2000 / (out["ms_per_step"] * 1e-3)) <= 1e-9 * out["value"]
+    assert out["verified"] is None and out["roofline"] is None and out["cpu_baseline"] is None and "legs" not in out
+
+
+def test_bench_dump_outputs_are_the_last_step_and_repeat_from_run_to_run(tmp_path):
+    """--dump-outputs: the depths and result types of the last timed step, identical in two runs with the same arguments,
+    every feature processed (no poison left) and equal to the CPU oracle on a frame of the step."""
+    from helpers import kitti_camera, run_oracle
+    from mono_lidar_depth_amd import capi, synth
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        _run(PLAIN + ["--dump-outputs", str(d)])
+    a, b = ({k: np.load(d / f"{k}.npy") for k in ("depth", "result_type")} for d in dirs)
+    assert a["depth"].dtype == np.float64 and a["result_type"].dtype == np.float32
+    assert a["depth"].shape == a["result_type"].shape == (32, 2000)
+    assert np.array_equal(a["depth"], b["depth"], equal_nan=True) and np.array_equal(a["result_type"], b["result_type"])
+    assert not (a["result_type"] == -77).any() and (a["result_type"] == 1).any()
+    # frame 5 of rank 0's sequence: cloud 5 % 4 of the resident set, feature set 5 (bench_support/resident.py)
+    cloud = synth.make_cloud(synth.HDL64, seed=0, frame=1)
+    uv = synth.make_features(2000, seed=5)
+    _, (d0, t0) = run_oracle(capi.params_c0(), cloud, uv, synth.make_ground_plane(cloud), kitti_camera())
+    assert np.array_equal(a["result_type"][5], t0.astype(np.float32))
+    assert np.allclose(a["depth"][5], d0, rtol=0, atol=1e-4, equal_nan=True)
 
 
 def test_bench_rccl_launch_wider_than_the_node_fails_fast():

@@ -1,8 +1,12 @@
 """The restatement against the reference's OWN object code, for the two translation units of the hot path that build
-without Eigen / PCL / OpenCV: Histogram.cpp and TresholdDepthGlobal.cpp (compiled from /root/reference by
-`make -C oracle ref` into oracle/_ref/, see oracle/ref_shim.cpp).  Nothing here reads /root/reference at run time; the
-tests are skipped where the library has not been built."""
+without Eigen / PCL / OpenCV: Histogram.cpp and TresholdDepthGlobal.cpp (compiled from the reference's sources by
+`make -C oracle ref` into oracle/_ref/, see oracle/ref_shim.cpp).  Nothing here reads the reference's tree at run time.
+Where the library has been built its answers are taken live and must equal the stored ones; elsewhere the answers it gave
+on exactly these inputs come from tests/golden/reference_parts.npz (written by tests/golden/make_reference_parts.py),
+looked up by a hash of the inputs, so an input that changes without the vectors being regenerated fails, never skips."""
 import ctypes as C
+import hashlib
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -11,14 +15,62 @@ from mono_lidar_depth_amd import capi
 from oracle import oracle
 
 ref = oracle.load_reference_parts()
-pytestmark = pytest.mark.skipif(ref is None, reason="oracle/_ref/libmld_ref.so not built (needs /root/reference)")
+GOLDEN = Path(__file__).resolve().parent / "golden" / "reference_parts.npz"
+RECORDED = {}   # every answer of the live library in this process (what make_reference_parts.py stores)
+_stored = None
+
+
+def _stored_answer(key):
+    global _stored
+    if _stored is None:
+        _stored = dict(np.load(GOLDEN)) if GOLDEN.exists() else {}
+    return _stored.get(key)
+
+
+def _key(kind, *arrays):
+    h = hashlib.sha1(kind.encode())
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return f"{kind}_{h.hexdigest()[:20]}"
+
+
+def _answer(key, live):
+    """The live library's answer (checked against the stored one, where that exists) or, without the library, the stored
+    answer for these inputs."""
+    stored = _stored_answer(key)
+    if ref is None:
+        assert stored is not None, f"{key}: no stored reference answer for these inputs (tests/golden/make_reference_parts.py)"
+        return stored
+    out = live()
+    RECORDED[key] = out
+    if stored is not None:
+        assert np.array_equal(stored, out), f"{key}: the reference library disagrees with its stored answer"
+    return out
 
 
 def _ref_counts(values, bin_width, bin_count):
     v = np.ascontiguousarray(values, dtype=np.float64)
-    out = np.zeros(bin_count, dtype=np.int32)
-    ref.ref_histogram_counts(v.ctypes.data, v.size, float(bin_width), int(bin_count), out.ctypes.data)
-    return out
+
+    def live():
+        out = np.zeros(bin_count, dtype=np.int32)
+        ref.ref_histogram_counts(v.ctypes.data, v.size, float(bin_width), int(bin_count), out.ctypes.data)
+        return out
+    return _answer(_key("hist", v, np.float64(bin_width), np.int64(bin_count)), live)
+
+
+def _ref_threshold(mode, min_value, max_value, depths):
+    """TresholdDepthGlobal(mode, min, max).CheckInDepth(d) for every d: (results, depths as updated in place)."""
+    d_in = np.ascontiguousarray(depths, dtype=np.float64)
+
+    def live():
+        out = np.empty((2, d_in.size), dtype=np.float64)
+        for i, d in enumerate(d_in):
+            dd = C.c_double(float(d))
+            out[0, i] = ref.ref_threshold_global(mode, min_value, max_value, C.byref(dd))
+            out[1, i] = dd.value
+        return out
+    out = _answer(_key("threshold", np.int64(mode), np.float64([min_value, max_value]), d_in), live)
+    return out[0].astype(np.int64), out[1]
 
 
 @pytest.mark.parametrize("bin_width,bin_count", [(0.3, 40), (0.1, 500), (1.0, 7), (2.5, 2), (0.3, 1)])
@@ -98,8 +150,7 @@ def test_global_threshold_equals_the_reference_class(mode):
     rng = np.random.default_rng(mode)
     P = capi.params_c0().replace(treshold_depth_mode=mode, treshold_depth_min=2, treshold_depth_max=60)
     depths = np.concatenate([rng.uniform(-10, 120, 3000), [2.0, 60.0, np.nextafter(2.0, 0), np.nextafter(60.0, 100), -1.0, 0.0]])
-    for d in depths:
+    r_ref, d_ref = _ref_threshold(mode, 2.0, 60.0, depths)
+    for d, r1, d1 in zip(depths, r_ref, d_ref):
         r0, d0 = oracle.threshold_global(P, float(d))
-        dd = C.c_double(float(d))
-        r1 = ref.ref_threshold_global(mode, 2.0, 60.0, C.byref(dd))
-        assert r0 == r1 and d0 == dd.value, d
+        assert r0 == r1 and d0 == d1, d
