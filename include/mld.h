@@ -480,6 +480,75 @@ int mld_tracklets_depths_device(mld_ctx* ctx, int n_seq, int bank_cur, int have_
                                 float* const* d_last_out, int32_t* const* type_cur_out, int32_t* const* type_last_out);
 
 /*
+ * The tracklet map of the batched layer, resident on the GPU — `_trackletMap` (std::map<int, feature_tracking::Tracklet>,
+ * a deque of (u, v, depth) per id) and the four places of TrackletDepthModule::process that touch it, for n_seq
+ * independent sequences per call:
+ *   mld_tracks_begin_device   ExractNewTrackletFrames' membership test `_trackletMap.count(id)`
+ *                             (tracklet_depth_module.cpp:23-61, :31): which ids of this frame are new
+ *   mld_tracks_commit_device  SaveFeatureDepths (:119-169) + TidyUpTracklets (:171-193) for the frame begun
+ *   mld_tracks_export_device  convert_tracklets_to_matches_msg (:209-259): the stored tracks in message order
+ *   mld_tracks_counts         the counters those functions return ((new, old) :60/:168, (success, failed) :258)
+ *   mld_tracklets_step_device begin -> mld_tracklets_depths_device with the store's masks -> commit: process()'s whole
+ *                             track side (:286-347) as ONE asynchronous chain; ids + features in, depths + histories out
+ * The store is bound to a context: it lives on that context's device and every call is asynchronous on that context's
+ * stream (mld_tracks_counts synchronises).  The host tables (arrays of n_seq device pointers / counts) are consumed
+ * before a call returns: a caller may queue many frames ahead of the device and reuse its host arrays.  The device
+ * arrays must stay valid until the work has run; the ids of a frame are read by its begin AND its commit.
+ * Like a context, a store serves one call at a time.
+ *
+ * mld_tracks_create: one map per sequence.
+ *   max_tracks : tracks per frame and sequence the store sustains indefinitely at any churn (every track replaced
+ *                every frame included): the rows of the tracks that ended are taken back before new ones are handed out.
+ *   max_history: >= 2; stored entries per track.  DEVIATION: the reference's deque is unbounded, here the oldest entries
+ *                fall off - results equal the reference whenever no track outlives max_history frames.
+ *   All memory is allocated here, none per frame.  Device bytes with cap = the power of two >= 2 * max_tracks:
+ *     n_seq * (max_tracks * (12 * max_history + 41) + 16 * cap + 132)
+ *   (histories 12 * max_history per track: 0.49 GB of 0.73 GB for 256 sequences x 10 000 tracks x 16 entries), plus
+ *   16 * 96 * n_seq bytes of pinned host memory.
+ *   Returns NULL on failure with the reason in *status_out (optional) and the text in mld_tracks_last_error(NULL).
+ *   Destroy the store before its context.
+ *
+ * mld_tracks_begin_device: ids[s] = n_tracks[s] int32 ids (`int id = tracklet.id`, :29; every int32 value is an id).
+ *   is_new_out[s][i] = 1 where ids[s][i] was not in the last committed frame of sequence s; is_new_out == NULL: the
+ *   masks go to buffers of the store (what mld_tracklets_step_device uses).  n_tracks[s] <= max_tracks, 0 allowed.
+ *   Ids must be unique within a sequence and frame: the reference's behaviour on a repeated id is an accident of
+ *   std::map::emplace; here one occurrence is stored (which one is unspecified), the others are counted
+ *   (mld_tracks_counts [5]) and export the stored occurrence's history.  A frame begun twice is begun afresh.
+ *
+ * mld_tracks_commit_device: per sequence the arrays of mld_tracklets_depths_device, d_cur / d_last being its outputs.
+ *   A track that is not new gets ((int)u_new, (int)v_new, d_cur) pushed to the front; a new one is created with
+ *   ((int)u_old, (int)v_old, d_last) and then gets the same push (length 2); u_old / v_old / d_last are read only there.
+ *   Every track of the previous frame that is absent from this one is erased: after a commit the live set is exactly
+ *   this frame's ids.  Coordinates are truncated as the reference's std::pair<int, int> does.
+ *
+ * mld_tracks_export_device: per sequence, for the tracks of the last committed frame in that frame's order:
+ *   len_out[s][i] = stored entries of track i; fp_out[s] = n_tracks x max_history x 3 float32 (u, v, d), newest first,
+ *   u / v the float of the stored integer (:237-238).  Entries at or beyond the length are NOT written (fixed stride: no
+ *   callee resize, no prefix sum).  Either table may be NULL.
+ *
+ * mld_tracks_counts: counts_out = n_seq x 6 int64 of the last committed frame: [0] live tracks, [1] created this frame,
+ *   [2] updated this frame, [3] stored features with d >= 0, [4] the other stored features, [5] repeated ids.
+ *
+ * mld_tracklets_step_device: arguments and bank convention as mld_tracklets_depths_device, with ids in place of is_new;
+ *   `tr` must have been created on `ctx` with the same n_seq.  The caller supplies feature_points[1] (u_old / v_old) for
+ *   every track; it is read only where the track turns out to be new.  d_last_out is written only there.  No
+ *   synchronisation, no host read of device data.
+ */
+typedef struct mld_tracks mld_tracks;
+mld_tracks* mld_tracks_create(mld_ctx* ctx, int n_seq, int64_t max_tracks, int max_history, int* status_out);
+void mld_tracks_destroy(mld_tracks* tr);
+const char* mld_tracks_last_error(const mld_tracks* tr);
+int mld_tracks_begin_device(mld_tracks* tr, const int32_t* const* ids, const int64_t* n_tracks, uint8_t* const* is_new_out);
+int mld_tracks_commit_device(mld_tracks* tr, const float* const* u_new, const float* const* v_new, const float* const* u_old,
+                             const float* const* v_old, const float* const* d_cur, const float* const* d_last);
+int mld_tracks_export_device(mld_tracks* tr, float* const* fp_out, int32_t* const* len_out);
+int mld_tracks_counts(mld_tracks* tr, int64_t* counts_out);
+int mld_tracklets_step_device(mld_ctx* ctx, mld_tracks* tr, int bank_cur, int have_last, const int32_t* const* ids,
+                              const float* const* u_new, const float* const* v_new, const float* const* u_old,
+                              const float* const* v_old, const int64_t* n_tracks, float* const* d_cur_out,
+                              float* const* d_last_out, int32_t* const* type_cur_out, int32_t* const* type_last_out);
+
+/*
  * Debug / parity getters (host buffers; each synchronises).
  *   mld_get_visible_count           -> _points_cs_image_visible.cols()         (DepthEstimator.cpp:192)
  *   mld_get_visible_image_points    -> getPointsCloudImageCs, 2 x Nvis col-major (:392-394)

@@ -1,0 +1,656 @@
+// mld_tracks.hip — the device-resident tracklet store of the batched tracklet layer (include/mld.h, "mld_tracks").
+//
+// TrackletDepthModule keeps `_trackletMap`, a std::map<int, Tracklet> whose values are deques of (u, v, depth)
+// (tracklets_depth/src/tracklet_depth_module.cpp): ExractNewTrackletFrames asks it which ids are new (:23-61),
+// SaveFeatureDepths pushes this frame's features to the front (:119-169), TidyUpTracklets erases every track without
+// an update (:171-193), convert_tracklets_to_matches_msg reads the tracks back in message order (:209-259).  Here the
+// map of every sequence lives in GPU memory and those four steps are kernels over all sequences at once.
+//
+// This translation unit uses the depth path through its public C-ABI only (mld_get_stream, mld_last_error,
+// mld_tracklets_depths_device); it shares no internals with mld_api.hip.
+//
+// Data, per sequence (everything allocated in mld_tracks_create):
+//   table[2][cap]      open-addressed id tables, cap = power of two >= 2 * max_tracks, linear probing.  A slot is
+//                      64 bits: bit 63 = occupied, bits 32..62 = history row, bits 0..31 = the id.  0 is "empty", so
+//                      every int32 is a legal id.  One table holds the last committed frame, the other is empty and
+//                      receives the next frame: a frame's live set is exactly its ids, so nothing is ever deleted
+//                      from a table that is probed (no tombstones).
+//   hist[max_tracks][max_history][3]   history rows, ring buffers of (float(int u), float(int v), d), with
+//   head[], len[]      the position of the newest entry and the number of stored entries of every row
+//   mark[]             the epoch (frame counter) of the last look-up that found the row's track
+//   free_rows[], top   the pool: a stack of unused rows
+//   row/slot/dup_row[2][max_tracks]    per track of the last committed / the pending frame: its row, its table slot
+//                      (-1: a repeated id that lost), and a row taken for a repeated id that has to go back to the pool
+//
+// Kernels, one launch over all sequences each (flat grid, block -> (sequence, chunk) through the block prefix in the
+// descriptors), ordered by kernel boundaries only:
+//   k_tracks_lookup    begin:  probe the committed table, write is_new and the row, stamp mark[row] = epoch
+//   k_tracks_release   commit: every track of the committed frame clears its slot (the table is empty afterwards) and,
+//                      if this frame did not stamp its row, pushes the row on the pool; clears the frame counters
+//   k_tracks_commit    commit: one thread per track: a new track pops a row, the track claims a slot of the other
+//                      table with atomicCAS, then pushes its entries
+//   k_tracks_export / k_tracks_count   read-only
+// Rows are released before they are taken and never in the same kernel, so max_tracks rows per sequence sustain
+// max_tracks tracks per frame at any churn, and the stack needs no ABA care.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../../include/mld.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kGens = 16;  // pinned generations of the descriptor table: the host may run this many uploads ahead
+constexpr unsigned long long kOccupied = 1ull << 63;
+
+// One sequence of one call.  Host-made, staged through the pinned ring, read by every kernel of the call.
+struct TrSeq {
+    const int32_t* ids;
+    uint8_t* is_new;
+    const float* u_new;
+    const float* v_new;
+    const float* u_old;
+    const float* v_old;
+    const float* d_cur;
+    const float* d_last;
+    float* fp_out;
+    int32_t* len_out;
+    int32_t n;          // tracks of the frame the call works on
+    int32_t n_prev;     // tracks of the committed frame (release pass)
+    int32_t blk0;       // first block of the sequence in a launch over n (export: over n * max_history)
+    int32_t blk0_prev;  // the same for the release pass (at least one block per sequence)
+};
+static_assert(sizeof(TrSeq) == 96 && sizeof(TrSeq) % 4 == 0, "the upload kernel moves 32-bit words");
+
+struct TrDev {
+    unsigned long long* table;  // [2][n_seq][cap]
+    float* hist;                // [n_seq][M][H][3]
+    int32_t* head;              // [n_seq][M]
+    int32_t* len;               // [n_seq][M]
+    uint32_t* mark;             // [n_seq][M]
+    int32_t* free_rows;         // [n_seq][M]
+    int32_t* top;               // [n_seq]
+    int32_t* row;               // [2][n_seq][M]
+    int32_t* slot;              // [2][n_seq][M]
+    int32_t* dup_row;           // [2][n_seq][M]
+    unsigned int* cnt;          // [n_seq][4]: new, old, repeated ids, tracks dropped for want of a row (never)
+    unsigned long long* feat;   // [n_seq][2]: stored features with d >= 0, the others
+    int32_t n_seq, M, H;
+    uint32_t cap;
+};
+
+__device__ __forceinline__ uint32_t hash_id(int32_t id) {  // (murmur3's finaliser)
+    uint32_t h = (uint32_t)id;
+    h ^= h >> 16;
+    h *= 0x85ebca6bu;
+    h ^= h >> 13;
+    h *= 0xc2b2ae35u;
+    h ^= h >> 16;
+    return h;
+}
+
+// The sequence a block belongs to: the last one whose first block is <= b (sequences without blocks share their
+// successor's first block and are skipped).
+template <bool kPrev>
+__device__ __forceinline__ int seq_of_block(const TrSeq* __restrict__ desc, int n_seq, int b) {
+    int lo = 0, hi = n_seq;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((kPrev ? desc[mid].blk0_prev : desc[mid].blk0) <= b) lo = mid + 1; else hi = mid;
+    }
+    return lo - 1;
+}
+
+__device__ __forceinline__ void wave_count(unsigned int* dst, bool pred) {
+    const unsigned long long m = __ballot(pred);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(dst, (unsigned int)__popcll(m));
+}
+
+__global__ __launch_bounds__(256) void k_tracks_upload(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src_host, int n_words) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n_words) dst[i] = __builtin_nontemporal_load(src_host + i);
+}
+
+__global__ __launch_bounds__(256) void k_tracks_init(TrDev T) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t total = (size_t)T.n_seq * T.M;
+    if (i < total) T.free_rows[i] = (int32_t)(i % (size_t)T.M);
+    if (i < (size_t)T.n_seq) T.top[i] = T.M;
+}
+
+// ExractNewTrackletFrames' `_trackletMap.count(id)` (:31) for every track of every sequence.
+__global__ __launch_bounds__(kBlock) void k_tracks_lookup(TrDev T, const TrSeq* __restrict__ desc, int prev, uint32_t epoch) {
+    const int s = seq_of_block<false>(desc, T.n_seq, (int)blockIdx.x);
+    const TrSeq& q = desc[s];
+    const int i = ((int)blockIdx.x - q.blk0) * kBlock + (int)threadIdx.x;
+    if (i >= q.n) return;
+    const int32_t id = q.ids[i];
+    const unsigned long long* __restrict__ tab = T.table + ((size_t)prev * T.n_seq + s) * T.cap;
+    const uint32_t mask = T.cap - 1;
+    uint32_t h = hash_id(id) & mask;
+    int row = -1;
+    for (uint32_t k = 0; k < T.cap; k++) {  // (the table is at most half full: an empty slot ends every chain)
+        const unsigned long long e = tab[h];
+        if (!(e & kOccupied)) break;
+        if ((uint32_t)e == (uint32_t)id) {
+            row = (int)((e >> 32) & 0x7fffffffu);
+            break;
+        }
+        h = (h + 1) & mask;
+    }
+    const size_t base = (size_t)s * T.M;
+    if (row >= 0) T.mark[base + row] = epoch;
+    T.row[((size_t)(1 - prev) * T.n_seq + s) * T.M + i] = row;
+    q.is_new[i] = row < 0 ? 1 : 0;
+}
+
+// A row back on the sequence's free stack.  (The stack cannot overflow - every row is released once; the test keeps a
+// miscount from ever becoming a store outside the array.)
+__device__ __forceinline__ void free_row(const TrDev& T, int s, int row) {
+    const int p = atomicAdd(&T.top[s], 1);
+    if (p >= 0 && p < T.M) T.free_rows[(size_t)s * T.M + p] = row;
+}
+
+// TidyUpTracklets (:171-193): the rows of the committed frame's tracks that the pending frame did not find go back to
+// the pool; the committed table is emptied slot by slot (its tracks know their slots).
+__global__ __launch_bounds__(kBlock) void k_tracks_release(TrDev T, const TrSeq* __restrict__ desc, int prev, uint32_t epoch) {
+    const int s = seq_of_block<true>(desc, T.n_seq, (int)blockIdx.x);
+    const TrSeq& q = desc[s];
+    const int i = ((int)blockIdx.x - q.blk0_prev) * kBlock + (int)threadIdx.x;
+    if (i < 4 && (int)blockIdx.x == q.blk0_prev) T.cnt[(size_t)s * 4 + i] = 0;
+    if (i >= q.n_prev) return;
+    const size_t ps = ((size_t)prev * T.n_seq + s) * T.M + i;
+    const size_t base = (size_t)s * T.M;
+    const int slot = T.slot[ps], row = T.row[ps], dup_row = T.dup_row[ps];
+    if (slot >= 0) {
+        T.table[((size_t)prev * T.n_seq + s) * T.cap + slot] = 0ull;
+        if (T.mark[base + row] != epoch) free_row(T, s, row);
+    }
+    if (dup_row >= 0) free_row(T, s, dup_row);
+}
+
+__device__ __forceinline__ void push_front(float* __restrict__ hr, int H, int& head, int& len, float u, float v, float d) {
+    head = head == 0 ? H - 1 : head - 1;
+    hr[head * 3 + 0] = u;
+    hr[head * 3 + 1] = v;
+    hr[head * 3 + 2] = d;
+    len = len < H ? len + 1 : H;
+}
+
+// SaveFeatureDepths (:119-169) into the table of the pending frame.
+__global__ __launch_bounds__(kBlock) void k_tracks_commit(TrDev T, const TrSeq* __restrict__ desc, int cur) {
+    const int s = seq_of_block<false>(desc, T.n_seq, (int)blockIdx.x);
+    const TrSeq& q = desc[s];
+    const int i = ((int)blockIdx.x - q.blk0) * kBlock + (int)threadIdx.x;
+    bool made = false, updated = false, repeated = false, dropped = false;
+    if (i < q.n) {
+        const size_t ps = ((size_t)cur * T.n_seq + s) * T.M + i;
+        const size_t base = (size_t)s * T.M;
+        int row = T.row[ps];
+        const bool fresh = row < 0;
+        if (fresh) {
+            const int t = atomicSub(&T.top[s], 1);
+            if (t > 0 && t <= T.M) {
+                row = T.free_rows[base + t - 1];
+            } else {  // (cannot happen: rows were released before, and n <= max_tracks)
+                atomicAdd(&T.top[s], 1);
+                dropped = true;
+            }
+        }
+        int slot = -1, dup_row = -1;
+        if (!dropped) {
+            const int32_t id = q.ids[i];
+            const unsigned long long mine = kOccupied | ((unsigned long long)(uint32_t)row << 32) | (uint32_t)id;
+            unsigned long long* tab = T.table + ((size_t)cur * T.n_seq + s) * T.cap;
+            const uint32_t mask = T.cap - 1;
+            uint32_t h = hash_id(id) & mask;
+            for (uint32_t k = 0; k < T.cap; k++) {
+                const unsigned long long old = atomicCAS(&tab[h], 0ull, mine);
+                if (old == 0ull) {
+                    slot = (int)h;
+                    break;
+                }
+                if ((uint32_t)old == (uint32_t)id) {  // the id occurs twice in this frame: the first claim stays
+                    repeated = true;
+                    if (fresh) dup_row = row;
+                    row = (int)((old >> 32) & 0x7fffffffu);
+                    break;
+                }
+                h = (h + 1) & mask;
+            }
+            if (slot < 0 && !repeated) {  // (a full table: cannot happen, cap >= 2 * max_tracks)
+                dropped = true;
+                if (fresh) dup_row = row;
+            }
+        }
+        if (slot >= 0) {
+            float* hr = T.hist + (base + row) * (size_t)T.H * 3;
+            int head = 0, len = 0;
+            if (fresh) {  // a new tracklet starts with the previous feature (:134-151)
+                push_front(hr, T.H, head, len, (float)(int)q.u_old[i], (float)(int)q.v_old[i], q.d_last[i]);
+                made = true;
+            } else {
+                head = T.head[base + row];
+                len = T.len[base + row];
+                updated = true;
+            }
+            push_front(hr, T.H, head, len, (float)(int)q.u_new[i], (float)(int)q.v_new[i], q.d_cur[i]);
+            T.head[base + row] = head;
+            T.len[base + row] = len;
+        }
+        T.row[ps] = dropped ? -1 : row;
+        T.slot[ps] = slot;
+        T.dup_row[ps] = dup_row;
+    }
+    unsigned int* cnt = T.cnt + (size_t)s * 4;
+    wave_count(cnt + 0, made);
+    wave_count(cnt + 1, updated);
+    wave_count(cnt + 2, repeated);
+    wave_count(cnt + 3, dropped);
+}
+
+// convert_tracklets_to_matches_msg (:209-259): one thread per (track, history position).
+__global__ __launch_bounds__(kBlock) void k_tracks_export(TrDev T, const TrSeq* __restrict__ desc, int cur) {
+    const int s = seq_of_block<false>(desc, T.n_seq, (int)blockIdx.x);
+    const TrSeq& q = desc[s];
+    const long long idx = ((long long)blockIdx.x - q.blk0) * kBlock + threadIdx.x;
+    const long long i = idx / T.H;
+    const int h = (int)(idx - i * T.H);
+    if (i >= q.n) return;
+    const size_t base = (size_t)s * T.M;
+    const int row = T.row[((size_t)cur * T.n_seq + s) * T.M + (size_t)i];
+    const int len = row >= 0 ? T.len[base + row] : 0;
+    if (h == 0 && q.len_out) q.len_out[i] = len;
+    if (h >= len || !q.fp_out) return;
+    int p = T.head[base + row] + h;
+    if (p >= T.H) p -= T.H;
+    const float* __restrict__ src = T.hist + ((base + row) * (size_t)T.H + p) * 3;
+    float* dst = q.fp_out + (size_t)idx * 3;
+    dst[0] = src[0];
+    dst[1] = src[1];
+    dst[2] = src[2];
+}
+
+// The (success, failed) pair of convert_tracklets_to_matches_msg (:235): stored features with depth >= 0 / the others.
+__global__ __launch_bounds__(kBlock) void k_tracks_count(TrDev T, const TrSeq* __restrict__ desc, int cur) {
+    const int s = seq_of_block<false>(desc, T.n_seq, (int)blockIdx.x);
+    const TrSeq& q = desc[s];
+    const int i = ((int)blockIdx.x - q.blk0) * kBlock + (int)threadIdx.x;
+    unsigned int good = 0, bad = 0;
+    if (i < q.n) {
+        const size_t ps = ((size_t)cur * T.n_seq + s) * T.M + i;
+        const size_t base = (size_t)s * T.M;
+        if (T.slot[ps] >= 0) {  // (a repeated id counts once)
+            const int row = T.row[ps];
+            const int len = T.len[base + row];
+            const float* __restrict__ hr = T.hist + (base + row) * (size_t)T.H * 3;
+            const int head = T.head[base + row];
+            for (int k = 0; k < len; k++) {
+                int p = head + k;
+                if (p >= T.H) p -= T.H;
+                if (hr[p * 3 + 2] >= 0.0f) good++; else bad++;
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        good += __shfl_down(good, off);
+        bad += __shfl_down(bad, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (good) atomicAdd(&T.feat[(size_t)s * 2 + 0], (unsigned long long)good);
+        if (bad) atomicAdd(&T.feat[(size_t)s * 2 + 1], (unsigned long long)bad);
+    }
+}
+
+char g_create_error[512] = "";
+
+}  // namespace
+
+struct mld_tracks {
+    mld_ctx* ctx = nullptr;
+    hipStream_t stream = nullptr;
+    int device = 0;
+    TrDev d{};
+    std::vector<void*> allocs;
+    uint8_t* own_mask = nullptr;  // [n_seq][M]: the masks of a begin without is_new_out
+    TrSeq* d_desc = nullptr;
+    unsigned char* up_base = nullptr;  // pinned: kGens generations of n_seq descriptors
+    size_t gen_bytes = 0;
+    hipEvent_t up_ev[kGens] = {};
+    bool up_busy[kGens] = {};
+    int up_next = 0;
+    // host-side frame state: everything a call needs is known when it is issued, nothing is read back
+    int committed = 0;      // the table / per-track arrays of the last committed frame
+    bool begun = false;
+    uint32_t epoch = 0;
+    std::vector<int32_t> n_committed, n_pending;
+    std::vector<const int32_t*> ids_pending;
+    std::vector<uint8_t*> mask_pending;
+    std::vector<TrSeq> stage;
+    std::vector<const uint8_t*> mask_table;  // mld_tracklets_step_device
+    std::string err;
+};
+
+namespace {
+
+int fail(mld_tracks* tr, int code, const char* text) {
+    tr->err = text;
+    return code;
+}
+
+#define TR_HIP(tr, expr)                                                                                   \
+    do {                                                                                                   \
+        const hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess) {                                                                            \
+            (tr)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                                 \
+            return MLD_ERR_HIP;                                                                            \
+        }                                                                                                  \
+    } while (0)
+
+// The staged descriptors to the device on the store's stream; `tr->stage` may be rewritten as soon as this returns.
+int upload(mld_tracks* tr) {
+    const size_t bytes = (size_t)tr->d.n_seq * sizeof(TrSeq);
+    const int g = tr->up_next;
+    if (tr->up_busy[g]) TR_HIP(tr, hipEventSynchronize(tr->up_ev[g]));
+    unsigned char* pinned = tr->up_base + (size_t)g * tr->gen_bytes;
+    std::memcpy(pinned, tr->stage.data(), bytes);
+    const int words = (int)(bytes / 4);
+    hipLaunchKernelGGL(k_tracks_upload, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, tr->stream,
+                       reinterpret_cast<uint32_t*>(tr->d_desc), reinterpret_cast<const uint32_t*>(pinned), words);
+    TR_HIP(tr, hipGetLastError());
+    TR_HIP(tr, hipEventRecord(tr->up_ev[g], tr->stream));
+    tr->up_busy[g] = true;
+    tr->up_next = (g + 1) % kGens;
+    return MLD_OK;
+}
+
+// Block prefixes of the staged descriptors: per sequence ceil(n * per_track / kBlock) blocks, and for the release pass
+// ceil(n_prev / kBlock) but at least one.  Returns the two totals.
+int layout_blocks(mld_tracks* tr, int per_track, int64_t* total, int64_t* total_prev) {
+    int64_t b = 0, bp = 0;
+    for (TrSeq& q : tr->stage) {
+        q.blk0 = (int32_t)b;
+        q.blk0_prev = (int32_t)bp;
+        b += ((int64_t)q.n * per_track + kBlock - 1) / kBlock;
+        bp += std::max<int64_t>(1, ((int64_t)q.n_prev + kBlock - 1) / kBlock);
+        if (b > 0x7fffffff || bp > 0x7fffffff) return fail(tr, MLD_ERR_CAPACITY, "more than 2^31 blocks in one launch");
+    }
+    *total = b;
+    *total_prev = bp;
+    return MLD_OK;
+}
+
+template <typename T>
+int dev_alloc(mld_tracks* tr, T** p, size_t count, bool zero) {
+    void* q = nullptr;
+    const size_t bytes = std::max<size_t>(count * sizeof(T), 4);
+    TR_HIP(tr, hipMalloc(&q, bytes));
+    tr->allocs.push_back(q);
+    if (zero) TR_HIP(tr, hipMemsetAsync(q, 0, bytes, tr->stream));
+    *p = static_cast<T*>(q);
+    return MLD_OK;
+}
+
+int allocate(mld_tracks* tr) {
+    TrDev& d = tr->d;
+    const size_t S = (size_t)d.n_seq, M = (size_t)d.M, H = (size_t)d.H;
+    int rc;
+    if ((rc = dev_alloc(tr, &d.table, 2 * S * d.cap, true))) return rc;
+    if ((rc = dev_alloc(tr, &d.hist, S * M * H * 3, false))) return rc;
+    if ((rc = dev_alloc(tr, &d.head, S * M, true))) return rc;
+    if ((rc = dev_alloc(tr, &d.len, S * M, true))) return rc;
+    if ((rc = dev_alloc(tr, &d.mark, S * M, true))) return rc;
+    if ((rc = dev_alloc(tr, &d.free_rows, S * M, false))) return rc;
+    if ((rc = dev_alloc(tr, &d.top, S, false))) return rc;
+    if ((rc = dev_alloc(tr, &d.row, 2 * S * M, true))) return rc;
+    if ((rc = dev_alloc(tr, &d.slot, 2 * S * M, true))) return rc;
+    if ((rc = dev_alloc(tr, &d.dup_row, 2 * S * M, true))) return rc;
+    if ((rc = dev_alloc(tr, &d.cnt, S * 4, true))) return rc;
+    if ((rc = dev_alloc(tr, &d.feat, S * 2, true))) return rc;
+    if ((rc = dev_alloc(tr, &tr->own_mask, S * M, true))) return rc;
+    if ((rc = dev_alloc(tr, &tr->d_desc, S, true))) return rc;
+    tr->gen_bytes = S * sizeof(TrSeq);
+    TR_HIP(tr, hipHostMalloc((void**)&tr->up_base, tr->gen_bytes * kGens, hipHostMallocDefault));
+    for (int g = 0; g < kGens; g++) TR_HIP(tr, hipEventCreateWithFlags(&tr->up_ev[g], hipEventDisableTiming));
+    const size_t total = std::max(S * M, S);
+    hipLaunchKernelGGL(k_tracks_init, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, tr->stream, d);
+    TR_HIP(tr, hipGetLastError());
+    return MLD_OK;
+}
+
+void release_all(mld_tracks* tr) {
+    if (tr->stream) (void)hipStreamSynchronize(tr->stream);
+    for (void* p : tr->allocs) (void)hipFree(p);
+    if (tr->up_base) (void)hipHostFree(tr->up_base);
+    for (int g = 0; g < kGens; g++)
+        if (tr->up_ev[g]) (void)hipEventDestroy(tr->up_ev[g]);
+    delete tr;
+}
+
+}  // namespace
+
+extern "C" {
+
+mld_tracks* mld_tracks_create(mld_ctx* ctx, int n_seq, int64_t max_tracks, int max_history, int* status_out) {
+    auto refuse = [&](int code, const char* text) -> mld_tracks* {
+        std::snprintf(g_create_error, sizeof(g_create_error), "%s", text);
+        if (status_out) *status_out = code;
+        return nullptr;
+    };
+    if (status_out) *status_out = MLD_OK;
+    // (the sizes first: they are refused without a look at the context)
+    if (n_seq < 1 || n_seq > 65536) return refuse(MLD_ERR_INVALID_ARG, "mld_tracks_create: n_seq must be in 1 .. 65536");
+    if (max_tracks < 1 || max_tracks > (1 << 24))
+        return refuse(MLD_ERR_INVALID_ARG, "mld_tracks_create: max_tracks must be in 1 .. 16777216");
+    if (max_history < 2 || max_history > 65535)
+        return refuse(MLD_ERR_INVALID_ARG, "mld_tracks_create: max_history must be in 2 .. 65535");
+    if (!ctx) return refuse(MLD_ERR_INVALID_ARG, "mld_tracks_create: null context");
+    mld_tracks* tr = new (std::nothrow) mld_tracks();
+    if (!tr) return refuse(MLD_ERR_HIP, "mld_tracks_create: out of host memory");
+    tr->ctx = ctx;
+    // the store lives on the context's stream and on that stream's device
+    tr->stream = static_cast<hipStream_t>(mld_get_stream(ctx));
+    hipDevice_t dev = 0;
+    if (hipStreamGetDevice(tr->stream, &dev) != hipSuccess || hipSetDevice((int)dev) != hipSuccess) {
+        delete tr;
+        return refuse(MLD_ERR_HIP, "mld_tracks_create: the device of the context's stream is not usable");
+    }
+    tr->device = (int)dev;
+    tr->d.n_seq = n_seq;
+    tr->d.M = (int32_t)max_tracks;
+    tr->d.H = max_history;
+    uint32_t cap = 2;
+    while (cap < 2u * (uint32_t)max_tracks) cap <<= 1;
+    tr->d.cap = cap;
+    tr->n_committed.assign((size_t)n_seq, 0);
+    tr->n_pending.assign((size_t)n_seq, 0);
+    tr->ids_pending.assign((size_t)n_seq, nullptr);
+    tr->mask_pending.assign((size_t)n_seq, nullptr);
+    tr->mask_table.assign((size_t)n_seq, nullptr);
+    tr->stage.assign((size_t)n_seq, TrSeq{});
+    const int rc = allocate(tr);
+    if (rc != MLD_OK) {
+        std::snprintf(g_create_error, sizeof(g_create_error), "mld_tracks_create: %s", tr->err.c_str());
+        if (status_out) *status_out = rc;
+        tr->stream = nullptr;  // (nothing of the store is in flight that the frees would not wait for)
+        release_all(tr);
+        return nullptr;
+    }
+    return tr;
+}
+
+void mld_tracks_destroy(mld_tracks* tr) {
+    if (!tr) return;
+    (void)hipSetDevice(tr->device);
+    release_all(tr);
+}
+
+const char* mld_tracks_last_error(const mld_tracks* tr) { return tr ? tr->err.c_str() : g_create_error; }
+
+int mld_tracks_begin_device(mld_tracks* tr, const int32_t* const* ids, const int64_t* n_tracks, uint8_t* const* is_new_out) {
+    if (!tr) return MLD_ERR_INVALID_ARG;
+    if (!ids || !n_tracks) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_begin_device: null table");
+    const int S = tr->d.n_seq;
+    for (int s = 0; s < S; s++) {
+        if (n_tracks[s] < 0) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_begin_device: negative track count");
+        if (n_tracks[s] > tr->d.M) return fail(tr, MLD_ERR_CAPACITY, "mld_tracks_begin_device: more tracks than max_tracks");
+        if (n_tracks[s] > 0 && (!ids[s] || (is_new_out && !is_new_out[s])))
+            return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_begin_device: null array");
+    }
+    TR_HIP(tr, hipSetDevice(tr->device));
+    for (int s = 0; s < S; s++) {
+        TrSeq& q = tr->stage[(size_t)s];
+        q = TrSeq{};
+        q.ids = ids[s];
+        q.is_new = is_new_out ? is_new_out[s] : tr->own_mask + (size_t)s * tr->d.M;
+        q.n = (int32_t)n_tracks[s];
+        q.n_prev = tr->n_committed[(size_t)s];
+        tr->n_pending[(size_t)s] = q.n;
+        tr->ids_pending[(size_t)s] = q.ids;
+        tr->mask_pending[(size_t)s] = q.is_new;
+    }
+    // a frame begun twice: the later look-up stamps a new epoch, the marks of the abandoned one mean nothing
+    tr->epoch++;
+    tr->begun = true;
+    int64_t blocks = 0, blocks_prev = 0;
+    int rc = layout_blocks(tr, 1, &blocks, &blocks_prev);
+    if (rc) return rc;
+    if (blocks == 0) return MLD_OK;
+    if ((rc = upload(tr))) return rc;
+    hipLaunchKernelGGL(k_tracks_lookup, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc, tr->committed,
+                       tr->epoch);
+    TR_HIP(tr, hipGetLastError());
+    return MLD_OK;
+}
+
+int mld_tracks_commit_device(mld_tracks* tr, const float* const* u_new, const float* const* v_new, const float* const* u_old,
+                             const float* const* v_old, const float* const* d_cur, const float* const* d_last) {
+    if (!tr) return MLD_ERR_INVALID_ARG;
+    if (!tr->begun) return fail(tr, MLD_ERR_NOT_INITIALIZED, "mld_tracks_commit_device without mld_tracks_begin_device");
+    if (!u_new || !v_new || !u_old || !v_old || !d_cur || !d_last)
+        return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_commit_device: null table");
+    const int S = tr->d.n_seq;
+    for (int s = 0; s < S; s++)
+        if (tr->n_pending[(size_t)s] > 0 && (!u_new[s] || !v_new[s] || !u_old[s] || !v_old[s] || !d_cur[s] || !d_last[s]))
+            return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_commit_device: null array");
+    TR_HIP(tr, hipSetDevice(tr->device));
+    for (int s = 0; s < S; s++) {
+        TrSeq& q = tr->stage[(size_t)s];
+        q = TrSeq{};
+        q.ids = tr->ids_pending[(size_t)s];
+        q.is_new = tr->mask_pending[(size_t)s];
+        q.u_new = u_new[s];
+        q.v_new = v_new[s];
+        q.u_old = u_old[s];
+        q.v_old = v_old[s];
+        q.d_cur = d_cur[s];
+        q.d_last = d_last[s];
+        q.n = tr->n_pending[(size_t)s];
+        q.n_prev = tr->n_committed[(size_t)s];
+    }
+    int64_t blocks = 0, blocks_prev = 0;
+    int rc = layout_blocks(tr, 1, &blocks, &blocks_prev);
+    if (rc) return rc;
+    if ((rc = upload(tr))) return rc;
+    hipLaunchKernelGGL(k_tracks_release, dim3((unsigned)blocks_prev), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc,
+                       tr->committed, tr->epoch);
+    TR_HIP(tr, hipGetLastError());
+    if (blocks > 0) {
+        hipLaunchKernelGGL(k_tracks_commit, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc,
+                           1 - tr->committed);
+        TR_HIP(tr, hipGetLastError());
+    }
+    tr->committed = 1 - tr->committed;
+    tr->n_committed = tr->n_pending;
+    tr->begun = false;
+    return MLD_OK;
+}
+
+int mld_tracks_export_device(mld_tracks* tr, float* const* fp_out, int32_t* const* len_out) {
+    if (!tr) return MLD_ERR_INVALID_ARG;
+    if (!fp_out && !len_out) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_export_device: nothing to write");
+    const int S = tr->d.n_seq;
+    for (int s = 0; s < S; s++)
+        if (tr->n_committed[(size_t)s] > 0 && ((fp_out && !fp_out[s]) || (len_out && !len_out[s])))
+            return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_export_device: null array");
+    TR_HIP(tr, hipSetDevice(tr->device));
+    for (int s = 0; s < S; s++) {
+        TrSeq& q = tr->stage[(size_t)s];
+        q = TrSeq{};
+        q.fp_out = fp_out ? fp_out[s] : nullptr;
+        q.len_out = len_out ? len_out[s] : nullptr;
+        q.n = tr->n_committed[(size_t)s];
+    }
+    int64_t blocks = 0, blocks_prev = 0;
+    int rc = layout_blocks(tr, tr->d.H, &blocks, &blocks_prev);
+    if (rc) return rc;
+    if (blocks == 0) return MLD_OK;
+    if ((rc = upload(tr))) return rc;
+    hipLaunchKernelGGL(k_tracks_export, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc, tr->committed);
+    TR_HIP(tr, hipGetLastError());
+    return MLD_OK;
+}
+
+int mld_tracks_counts(mld_tracks* tr, int64_t* counts_out) {
+    if (!tr) return MLD_ERR_INVALID_ARG;
+    if (!counts_out) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_counts: null output");
+    const int S = tr->d.n_seq;
+    TR_HIP(tr, hipSetDevice(tr->device));
+    for (int s = 0; s < S; s++) {
+        TrSeq& q = tr->stage[(size_t)s];
+        q = TrSeq{};
+        q.n = tr->n_committed[(size_t)s];
+    }
+    int64_t blocks = 0, blocks_prev = 0;
+    int rc = layout_blocks(tr, 1, &blocks, &blocks_prev);
+    if (rc) return rc;
+    TR_HIP(tr, hipMemsetAsync(tr->d.feat, 0, (size_t)S * 2 * sizeof(unsigned long long), tr->stream));
+    if (blocks > 0) {
+        if ((rc = upload(tr))) return rc;
+        hipLaunchKernelGGL(k_tracks_count, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc, tr->committed);
+        TR_HIP(tr, hipGetLastError());
+    }
+    std::vector<unsigned int> cnt((size_t)S * 4);
+    std::vector<unsigned long long> feat((size_t)S * 2);
+    TR_HIP(tr, hipMemcpyAsync(cnt.data(), tr->d.cnt, cnt.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, tr->stream));
+    TR_HIP(tr, hipMemcpyAsync(feat.data(), tr->d.feat, feat.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, tr->stream));
+    TR_HIP(tr, hipStreamSynchronize(tr->stream));
+    for (int s = 0; s < S; s++) {
+        int64_t* c = counts_out + (size_t)s * 6;
+        c[1] = cnt[(size_t)s * 4 + 0];
+        c[2] = cnt[(size_t)s * 4 + 1];
+        c[0] = c[1] + c[2];
+        c[3] = (int64_t)feat[(size_t)s * 2 + 0];
+        c[4] = (int64_t)feat[(size_t)s * 2 + 1];
+        c[5] = cnt[(size_t)s * 4 + 2];
+    }
+    return MLD_OK;
+}
+
+int mld_tracklets_step_device(mld_ctx* ctx, mld_tracks* tr, int bank_cur, int have_last, const int32_t* const* ids,
+                              const float* const* u_new, const float* const* v_new, const float* const* u_old,
+                              const float* const* v_old, const int64_t* n_tracks, float* const* d_cur_out,
+                              float* const* d_last_out, int32_t* const* type_cur_out, int32_t* const* type_last_out) {
+    if (!tr) return MLD_ERR_INVALID_ARG;
+    if (!ctx || ctx != tr->ctx) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracklets_step_device: the store belongs to another context");
+    if (!d_cur_out || !d_last_out) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracklets_step_device: null output table");
+    int rc = mld_tracks_begin_device(tr, ids, n_tracks, nullptr);
+    if (rc) return rc;
+    for (int s = 0; s < tr->d.n_seq; s++) tr->mask_table[(size_t)s] = tr->mask_pending[(size_t)s];
+    rc = mld_tracklets_depths_device(ctx, tr->d.n_seq, bank_cur, have_last, u_new, v_new, u_old, v_old, tr->mask_table.data(),
+                                     n_tracks, d_cur_out, d_last_out, type_cur_out, type_last_out);
+    if (rc) {  // (the frame stays begun and uncommitted: the next begin replaces it)
+        tr->err = std::string("mld_tracklets_depths_device: ") + mld_last_error(ctx);
+        return rc;
+    }
+    return mld_tracks_commit_device(tr, u_new, v_new, u_old, v_old, d_cur_out, d_last_out);
+}
+
+}  // extern "C"

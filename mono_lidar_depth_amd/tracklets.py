@@ -8,7 +8,9 @@ What runs on the GPU: the feature gather (newest feature of every track, previou
 to integer pixels), both CalculateDepth calls and the float32 scatter — one C-ABI call, `mld_tracklets_depth*`.
 The previous frame is NOT re-projected as the reference does (:115 -> setInputCloud): its frame slot (cloud, pixel
 map, ground plane) is kept and the two slots ping-pong.  The tracklet map itself (ids seen so far, per-track
-history) is host bookkeeping, kept here in Python.
+history) is host bookkeeping in the one-frame TrackletDepthModule, kept here in Python; at batch size it lives on the
+GPU: TrackletStore (mld_tracks_*) decides the new tracks, keeps the histories, drops the dead tracks and exports the
+stored tracks in message order, and TrackletBatch.step runs a whole frame of every sequence with it.
 """
 from __future__ import annotations
 
@@ -18,8 +20,8 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from . import capi
-from .depth_estimator import (NO_PLANE, CameraPinhole, DepthEstimator, ExceptionPclInvalid, GroundPlane, RansacPlane,
-                              SemanticPlane, _is_torch_cuda)
+from .depth_estimator import (NO_PLANE, CameraPinhole, DepthEstimator, DepthEstimatorError, ExceptionPclInvalid,
+                              GroundPlane, RansacPlane, SemanticPlane, _is_torch_cuda)
 
 
 class TrackletDepthModule:
@@ -157,11 +159,81 @@ class TrackletDepthModule:
         return list(self._tracklet_map[track_id])
 
 
+class TrackletStore:
+    """`_trackletMap` of S independent sequences in GPU memory (mld_tracks_*, include/mld.h): begin = which ids are new
+    (ExractNewTrackletFrames :23-61), commit = SaveFeatureDepths + TidyUpTracklets (:119-193), export =
+    convert_tracklets_to_matches_msg (:209-259).  Histories hold at most `max_history` entries per track (the
+    reference's deque is unbounded).  Lists of S torch CUDA tensors in and out; asynchronous on the estimator's stream,
+    only counts() synchronises.  Close the store before its estimator."""
+
+    COUNT_NAMES = ("live", "new", "old", "features_ok", "features_failed", "duplicates")
+
+    def __init__(self, estimator: DepthEstimator, n_seq: int, max_tracks: int, max_history: int):
+        self._est, self._lib = estimator, estimator._lib
+        self.S, self.max_tracks, self.max_history = int(n_seq), int(max_tracks), int(max_history)
+        st = C.c_int(0)
+        self._tr = self._lib.mld_tracks_create(estimator._ctx, self.S, self.max_tracks, self.max_history, C.byref(st))
+        if not self._tr:
+            raise DepthEstimatorError(st.value, self._lib.mld_tracks_last_error(None).decode())
+        self._keep = {}
+
+    def _check(self, rc: int):
+        if rc != capi.MLD_OK:
+            raise DepthEstimatorError(rc, self._lib.mld_tracks_last_error(self._tr).decode())
+
+    def _vp(self, ts):
+        if ts is None:
+            return None
+        if len(ts) != self.S:
+            raise ValueError(f"expected {self.S} tensors, one per sequence")
+        return (C.c_void_p * self.S)(*[int(t.data_ptr()) for t in ts])
+
+    def begin(self, ids, is_new_out=None):
+        """ids: S int32 CUDA tensors; is_new_out: S uint8 CUDA tensors of the same lengths, or None (masks kept in
+        the store).  The ids are read again by commit()."""
+        self._check(self._lib.mld_tracks_begin_device(self._tr, self._vp(ids), (C.c_int64 * self.S)(*[int(t.shape[0]) for t in ids]),
+                                                      self._vp(is_new_out)))
+        self._keep["begin"] = (list(ids), list(is_new_out) if is_new_out is not None else None)
+
+    def commit(self, u_new, v_new, u_old, v_old, d_cur, d_last):
+        """S float32 CUDA tensors each, indexed as the ids of begin(); d_cur / d_last: the depths of
+        mld_tracklets_depths_device (d_last is read where the track is new)."""
+        arrs = (u_new, v_new, u_old, v_old, d_cur, d_last)
+        self._check(self._lib.mld_tracks_commit_device(self._tr, *[self._vp(a) for a in arrs]))
+        self._keep["commit"] = [list(a) for a in arrs]
+
+    def export(self, fp_out, len_out):
+        """fp_out: S float32 CUDA tensors [n_tracks, max_history, 3] ((u, v, d), newest first; rows beyond a track's
+        length stay untouched), len_out: S int32 CUDA tensors [n_tracks]; the tracks of the last committed frame."""
+        self._check(self._lib.mld_tracks_export_device(self._tr, self._vp(fp_out), self._vp(len_out)))
+        self._keep["export"] = (fp_out, len_out)
+
+    def counts(self) -> np.ndarray:
+        """[S, 6] int64 of the last committed frame, columns COUNT_NAMES.  Synchronises."""
+        out = np.zeros((self.S, 6), dtype=np.int64)
+        self._check(self._lib.mld_tracks_counts(self._tr, out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
+
+    def close(self):
+        if self._tr:
+            self._lib.mld_tracks_destroy(self._tr)
+            self._tr = None
+        self._keep = {}
+
+    def __del__(self):
+        try:
+            if self._est._ctx is not None:  # (the estimator took the stream with it otherwise)
+                self.close()
+        except Exception:
+            pass
+
+
 class TrackletBatch:
     """The tracklet layer for S independent sequences at once (mld_set_clouds_planes_range_device +
     mld_tracklets_depths_device): the estimator's frame slots are two banks of S slots, sequence s keeps its current
     frame in slot bank * S + s and its previous frame, still resident, in the other bank.  Device tensors in, device
-    tensors out; asynchronous.  (Track bookkeeping per sequence is the caller's, as in TrackletDepthModule.)"""
+    tensors out; asynchronous.  run() takes the new-track masks from the caller, who then keeps the tracklet maps
+    (as TrackletDepthModule does); step() takes the track ids and keeps the maps on the GPU in a TrackletStore."""
 
     def __init__(self, parameters, camera: CameraPinhole, transform_lidar_to_cam, n_seq: int, max_tracks: int,
                  device: int = 0, list_capacity=None):
@@ -174,6 +246,49 @@ class TrackletBatch:
         self.bank = 0
         self.have_last = False
         self._keep = None
+        self.max_tracks = int(max_tracks)
+        self.store: Optional[TrackletStore] = None
+
+    def attach_store(self, max_history: int) -> TrackletStore:
+        """The GPU-resident tracklet maps of the S sequences that step() works on."""
+        if self.store is None:
+            self.store = TrackletStore(self.est, self.S, self.max_tracks, max_history)
+        return self.store
+
+    def prepare_step(self, clouds, coeffs, masks, ids, u_new, v_new, u_old, v_old, d_cur, d_last, t_cur=None, t_last=None):
+        """Pointer tables of one frame of every sequence for step(): as prepare(), with the S int32 CUDA tensors of
+        track ids in place of the new-track masks."""
+        S = self.S
+        vp = lambda ts: (C.c_void_p * S)(*[int(t.data_ptr()) for t in ts])  # noqa: E731
+        co = np.ascontiguousarray(coeffs, dtype=np.float32).reshape(S, 4)
+        return {"clouds": vp(clouds), "n": (C.c_int64 * S)(*[int(c.shape[0]) for c in clouds]), "coeffs": co,
+                "masks": vp(masks), "ids": vp(ids), "u_new": vp(u_new), "v_new": vp(v_new), "u_old": vp(u_old),
+                "v_old": vp(v_old), "nt": (C.c_int64 * S)(*[int(t.shape[0]) for t in ids]), "d_cur": vp(d_cur),
+                "d_last": vp(d_last), "t_cur": vp(t_cur) if t_cur is not None else None,
+                "t_last": vp(t_last) if t_last is not None else None,
+                "keep": (list(clouds), list(masks), list(ids), list(u_new), list(v_new), list(u_old), list(v_old),
+                         list(d_cur), list(d_last), t_cur, t_last)}
+
+    def step(self, f, nxt: Optional["TrackletBatch"] = None, handover: str = "projection"):
+        """run() with the tracklet maps on the GPU (mld_tracklets_step_device): projection of the current bank, then
+        new-track decision -> depths -> histories as one asynchronous chain.  `f` from prepare_step(); attach_store()
+        first.  The histories are read with store.export(...)."""
+        if self.store is None:
+            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.step without attach_store")
+        S, est, lib = self.S, self.est, self.est._lib
+        est._check(lib.mld_set_clouds_planes_range_device(est._ctx, self.bank * S, S, f["clouds"], f["n"], 16,
+                                                          f["coeffs"].ctypes.data_as(C.POINTER(C.c_float)), f["masks"]))
+        if nxt is not None and nxt is not self:
+            if handover == "classify":
+                nxt.est.orderAfterClassify(est)
+            else:
+                nxt.est.orderAfter(est)
+        self.store._check(lib.mld_tracklets_step_device(est._ctx, self.store._tr, self.bank, 1 if self.have_last else 0,
+                                                        f["ids"], f["u_new"], f["v_new"], f["u_old"], f["v_old"], f["nt"],
+                                                        f["d_cur"], f["d_last"], f["t_cur"], f["t_last"]))
+        self._keep = (self._keep[1] if self._keep else None, f)
+        self.bank = 1 - self.bank
+        self.have_last = True
 
     def prepare(self, clouds, coeffs, masks, u_new, v_new, u_old, v_old, is_new, d_cur, d_last, t_cur=None, t_last=None):
         """Pointer tables of one frame of every sequence (reusable: a steady-state caller prepares one per bank).
@@ -217,4 +332,7 @@ class TrackletBatch:
         self.run(self.prepare(clouds, *args, **kw))
 
     def close(self):
+        if self.store is not None:
+            self.store.close()
+            self.store = None
         self.est.close()
