@@ -549,6 +549,66 @@ int mld_tracklets_step_device(mld_ctx* ctx, mld_tracks* tr, int bank_cur, int ha
                               float* const* d_last_out, int32_t* const* type_cur_out, int32_t* const* type_last_out);
 
 /*
+ * Per-track semantic labels for a batch — matches_conversion_ros_tool's `semantic_labels` node, assignLabels
+ * (src/semantic_labels/semantic_labels.cpp:50-72), which the reference's launch files run directly behind
+ * tracklets_depth: for every track, the most frequent label of a mono8 label image in a window around the newest
+ * feature point goes into TrackletWithOutlierFlag.label.  n_seq independent sequences per call, every array in GPU
+ * memory.  (There is no host-pointer, one-frame form: see INTEGRATION.md.)
+ *
+ * Per track, with p = ((int)u, (int)v) - C++ truncation toward zero, -0.7 -> 0 - and INTEGER roi_width / 2,
+ * roi_height / 2 (:56-60):
+ *   columns [max(0, p.x - roi_width / 2),  min(cols, p.x + roi_width / 2))
+ *   rows    [max(0, p.y - roi_height / 2), min(rows, p.y + roi_height / 2))
+ * The window is 2 * (roi_width / 2) x 2 * (roi_height / 2) pixels, offset toward the upper left: the default roi 5 x 5
+ * counts 4 x 4 pixels, columns p.x - 2 .. p.x + 1.  This is the reference's arithmetic and is kept.  The label is the
+ * uchar value with the highest count in the window.
+ *
+ * Where the reference is undefined, this is defined:
+ *   DEVIATION (ties): the reference takes std::max_element over a std::unordered_map, so among equally frequent labels
+ *     the library's bucket order decides.  Here the SMALLEST label value among the most frequent wins.
+ *   DEVIATION (empty window): roi_width / 2 == 0 or roi_height / 2 == 0, or a point so far outside the image that
+ *     min >= max - OpenCV asserts on start > end and the reference dereferences end() on start == end.  Here the label
+ *     is -2, the value matches_msg_conversions_ros/convert.hpp:53,97 gives every track before this node runs.
+ *   DEVIATION (u or v not convertible): NaN, +-inf and values beyond the range of int are undefined behaviour in the
+ *     reference's float -> int conversion.  Here they are an empty window (-2).  Everything else behaves as if computed
+ *     in exact integer arithmetic: p +- roi / 2 does not overflow for any finite float and any roi >= 0.
+ * Where none of the three applies the answer is unique and is the reference's.
+ *
+ * mld_labels_create: an object bound to `ctx` for calls of n_seq (1 .. 65536) sequences.  It owns 48 * n_seq bytes of
+ *   device memory and 16 * 48 * n_seq bytes of pinned host memory (the descriptor ring); nothing is allocated per call.
+ *   The size is checked before the context is looked at.  Returns NULL on failure with the reason in *status_out
+ *   (optional) and the text in mld_labels_last_error(NULL).  Destroy the object before its context.
+ *
+ * mld_labels_assign_device: tables of n_seq entries.
+ *   label_image_dev[s]  the image of sequence s: rows x cols uint8, row_stride_bytes >= cols between rows; neither the
+ *                       base nor the stride needs any alignment.  One geometry for all sequences; rows, cols >= 1,
+ *                       rows * cols < 2^31.
+ *   roi_width, roi_height  >= 0, no upper limit (the window is clipped to the image).
+ *   u[s], v[s]          n_tracks[s] float32 each: the newest feature of every track in the frame's order - the arrays
+ *                       handed to mld_tracklets_step_device as u_new / v_new.  (The store keeps (float)(int)u, and
+ *                       truncating that again gives the same pixel: labels of the raw features and of an exported
+ *                       history's entry 0 are equal.)
+ *   n_tracks[s]         >= 0; a sequence without tracks needs no arrays.
+ *   label_out[s][i]     int16 as TrackletWithOutlierFlag.label: 0 .. 255, or -2.
+ *   votes_out           optional - the table or single entries may be NULL.  votes_out[s] = n_tracks[s] x 2 int32: the
+ *                       winner's count and the number of pixels of the clipped window (0, 0 for an empty one), so that
+ *                       a caller can discard weak majorities.
+ *   Asynchronous on the context's stream: no synchronisation, no host read of device data.  The host tables are
+ *   consumed before the call returns; the device arrays must stay valid until the work has run.  Like a context, the
+ *   object serves one call at a time.  MLD_ERR_INVALID_ARG with a text naming the argument (mld_labels_last_error; of
+ *   NULL for a null object) on: a null object, a null table other than votes_out, a null array of a sequence that has
+ *   tracks, rows or cols < 1, row_stride_bytes < cols, a negative roi, a negative n_tracks.
+ */
+typedef struct mld_labels mld_labels;
+mld_labels* mld_labels_create(mld_ctx* ctx, int n_seq, int* status_out);
+void mld_labels_destroy(mld_labels* lb);
+const char* mld_labels_last_error(const mld_labels* lb);
+int mld_labels_assign_device(mld_labels* lb, const uint8_t* const* label_image_dev, int rows, int cols,
+                             int row_stride_bytes, int roi_width, int roi_height, const float* const* u,
+                             const float* const* v, const int64_t* n_tracks, int16_t* const* label_out,
+                             int32_t* const* votes_out);
+
+/*
  * Debug / parity getters (host buffers; each synchronises).
  *   mld_get_visible_count           -> _points_cs_image_visible.cols()         (DepthEstimator.cpp:192)
  *   mld_get_visible_image_points    -> getPointsCloudImageCs, 2 x Nvis col-major (:392-394)

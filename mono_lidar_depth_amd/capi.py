@@ -199,6 +199,11 @@ _SIGNATURES = [
     ("mld_tracks_counts", C.c_int, [C.c_void_p, _P(C.c_int64)]),
     ("mld_tracklets_step_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [_P(C.c_void_p)] * 5 +
      [_P(C.c_int64)] + [_P(C.c_void_p)] * 4),
+    ("mld_labels_create", C.c_void_p, [C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("mld_labels_destroy", None, [C.c_void_p]),
+    ("mld_labels_last_error", C.c_char_p, [C.c_void_p]),
+    ("mld_labels_assign_device", C.c_int, [C.c_void_p, _P(C.c_void_p)] + [C.c_int] * 5 + [_P(C.c_void_p)] * 2 +
+     [_P(C.c_int64)] + [_P(C.c_void_p)] * 2),
     ("mld_get_visible_count", C.c_int, [C.c_void_p, C.c_int, _P(C.c_int64)]),
     ("mld_get_visible_image_points", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
     ("mld_get_point_index", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),

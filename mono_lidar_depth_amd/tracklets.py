@@ -10,7 +10,9 @@ The previous frame is NOT re-projected as the reference does (:115 -> setInputCl
 map, ground plane) is kept and the two slots ping-pong.  The tracklet map itself (ids seen so far, per-track
 history) is host bookkeeping in the one-frame TrackletDepthModule, kept here in Python; at batch size it lives on the
 GPU: TrackletStore (mld_tracks_*) decides the new tracks, keeps the histories, drops the dead tracks and exports the
-stored tracks in message order, and TrackletBatch.step runs a whole frame of every sequence with it.
+stored tracks in message order, and TrackletBatch.step runs a whole frame of every sequence with it.  SemanticLabels
+(mld_labels_*) is the node that follows tracklets_depth in the reference's launch files: the label of every track by
+majority vote in a window of a label image (matches_conversion_ros_tool, semantic_labels.cpp:50-72).
 """
 from __future__ import annotations
 
@@ -228,6 +230,66 @@ class TrackletStore:
             pass
 
 
+class SemanticLabels:
+    """assignLabels (matches_conversion_ros_tool/src/semantic_labels/semantic_labels.cpp:50-72) for S sequences per call
+    (mld_labels_*, include/mld.h - the window arithmetic and the three defined cases are stated there).  Lists of S
+    torch CUDA tensors in and out; asynchronous on the estimator's stream.  Close it before its estimator."""
+
+    NO_LABEL = -2
+
+    def __init__(self, estimator: DepthEstimator, n_seq: int):
+        self._est, self._lib = estimator, estimator._lib
+        self.S = int(n_seq)
+        st = C.c_int(0)
+        self._lb = self._lib.mld_labels_create(estimator._ctx, self.S, C.byref(st))
+        if not self._lb:
+            raise DepthEstimatorError(st.value, self._lib.mld_labels_last_error(None).decode())
+        self._keep = None
+
+    def assign(self, images, roi, u, v, label_out, votes_out=None):
+        """images: S uint8 CUDA tensors [rows, cols] of one shape and row stride (unit column stride); roi: (width,
+        height); u, v: S float32 CUDA tensors, the newest feature of every track; label_out: S int16 CUDA tensors of
+        the same lengths; votes_out: None, or S int32 CUDA tensors [n, 2] (single entries may be None) that receive
+        (count of the winning label, pixels in the clipped window)."""
+        S = self.S
+        for name, ts in (("images", images), ("u", u), ("v", v), ("label_out", label_out), ("votes_out", votes_out)):
+            if ts is not None and len(ts) != S:
+                raise ValueError(f"{name}: expected {S} tensors, one per sequence")
+        rows, cols = (int(x) for x in images[0].shape)
+        stride = int(images[0].stride(0))
+        for im in images:
+            if tuple(im.shape) != (rows, cols) or (rows > 1 and int(im.stride(0)) != stride) or int(im.stride(1)) != 1:
+                raise ValueError("images: one shape and row stride for all sequences, unit column stride")
+        for s in range(S):
+            n = int(u[s].shape[0])
+            if int(v[s].shape[0]) != n or int(label_out[s].shape[0]) != n:
+                raise ValueError(f"sequence {s}: u, v and label_out differ in length")
+            if votes_out is not None and votes_out[s] is not None and tuple(votes_out[s].shape) != (n, 2):
+                raise ValueError(f"sequence {s}: votes_out must be [{n}, 2]")
+        vp = lambda ts: (C.c_void_p * S)(*[int(t.data_ptr()) if t is not None else None for t in ts])  # noqa: E731
+        rc = self._lib.mld_labels_assign_device(self._lb, vp(images), rows, cols, max(stride, cols), int(roi[0]), int(roi[1]),
+                                                vp(u), vp(v), (C.c_int64 * S)(*[int(t.shape[0]) for t in u]), vp(label_out),
+                                                vp(votes_out) if votes_out is not None else None)
+        if rc != capi.MLD_OK:
+            raise DepthEstimatorError(rc, self._lib.mld_labels_last_error(self._lb).decode())
+        # the arrays must outlive the asynchronous launch (the previous call's as well: it may still be queued)
+        now = (list(images), list(u), list(v), list(label_out), list(votes_out) if votes_out is not None else None)
+        self._keep = (self._keep[1] if self._keep else None, now)
+
+    def close(self):
+        if self._lb:
+            self._lib.mld_labels_destroy(self._lb)
+            self._lb = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            if self._est._ctx is not None:  # (the estimator took the stream with it otherwise)
+                self.close()
+        except Exception:
+            pass
+
+
 class TrackletBatch:
     """The tracklet layer for S independent sequences at once (mld_set_clouds_planes_range_device +
     mld_tracklets_depths_device): the estimator's frame slots are two banks of S slots, sequence s keeps its current
@@ -248,6 +310,22 @@ class TrackletBatch:
         self._keep = None
         self.max_tracks = int(max_tracks)
         self.store: Optional[TrackletStore] = None
+        self.semantic_labels: Optional[SemanticLabels] = None
+
+    def attach_labels(self) -> SemanticLabels:
+        """The label assignment of the S sequences that labels() queues behind a step."""
+        if self.semantic_labels is None:
+            self.semantic_labels = SemanticLabels(self.est, self.S)
+        return self.semantic_labels
+
+    def labels(self, f, images, roi, label_out, votes_out=None):
+        """The labels of the tracks of table `f` (prepare_step() / prepare()), queued on the estimator's stream - behind
+        the step() / run() of `f` when called after it: SemanticLabels.assign on the table's u_new / v_new.
+        attach_labels() first."""
+        if self.semantic_labels is None:
+            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.labels without attach_labels")
+        u_new, v_new = f["features"]
+        self.semantic_labels.assign(images, roi, u_new, v_new, label_out, votes_out)
 
     def attach_store(self, max_history: int) -> TrackletStore:
         """The GPU-resident tracklet maps of the S sequences that step() works on."""
@@ -267,7 +345,8 @@ class TrackletBatch:
                 "d_last": vp(d_last), "t_cur": vp(t_cur) if t_cur is not None else None,
                 "t_last": vp(t_last) if t_last is not None else None,
                 "keep": (list(clouds), list(masks), list(ids), list(u_new), list(v_new), list(u_old), list(v_old),
-                         list(d_cur), list(d_last), t_cur, t_last)}
+                         list(d_cur), list(d_last), t_cur, t_last),
+                "features": (list(u_new), list(v_new))}
 
     def step(self, f, nxt: Optional["TrackletBatch"] = None, handover: str = "projection"):
         """run() with the tracklet maps on the GPU (mld_tracklets_step_device): projection of the current bank, then
@@ -304,7 +383,8 @@ class TrackletBatch:
                 "d_last": vp(d_last), "t_cur": vp(t_cur) if t_cur is not None else None,
                 "t_last": vp(t_last) if t_last is not None else None,
                 "keep": (list(clouds), list(masks), list(u_new), list(v_new), list(u_old), list(v_old), list(is_new),
-                         list(d_cur), list(d_last), t_cur, t_last)}
+                         list(d_cur), list(d_last), t_cur, t_last),
+                "features": (list(u_new), list(v_new))}
 
     def run(self, f, nxt: Optional["TrackletBatch"] = None, handover: str = "projection"):
         """One frame of every sequence from prepared tables: projection of the current bank, then the tracklet call.
@@ -332,6 +412,9 @@ class TrackletBatch:
         self.run(self.prepare(clouds, *args, **kw))
 
     def close(self):
+        if self.semantic_labels is not None:
+            self.semantic_labels.close()
+            self.semantic_labels = None
         if self.store is not None:
             self.store.close()
             self.store = None
