@@ -487,6 +487,8 @@ int mld_tracklets_depths_device(mld_ctx* ctx, int n_seq, int bank_cur, int have_
  *                             (tracklet_depth_module.cpp:23-61, :31): which ids of this frame are new
  *   mld_tracks_commit_device  SaveFeatureDepths (:119-169) + TidyUpTracklets (:171-193) for the frame begun
  *   mld_tracks_export_device  convert_tracklets_to_matches_msg (:209-259): the stored tracks in message order
+ *   mld_tracks_export_packed_device  the same tracks back to back, every track with exactly its stored entries, and
+ *                             the offsets at which they start (what the message holds: `curTracklet.size()` points each)
  *   mld_tracks_counts         the counters those functions return ((new, old) :60/:168, (success, failed) :258)
  *   mld_tracklets_step_device begin -> mld_tracklets_depths_device with the store's masks -> commit: process()'s whole
  *                             track side (:286-347) as ONE asynchronous chain; ids + features in, depths + histories out
@@ -502,8 +504,10 @@ int mld_tracklets_depths_device(mld_ctx* ctx, int n_seq, int bank_cur, int have_
  *   max_history: >= 2; stored entries per track.  DEVIATION: the reference's deque is unbounded, here the oldest entries
  *                fall off - results equal the reference whenever no track outlives max_history frames.
  *   All memory is allocated here, none per frame.  Device bytes with cap = the power of two >= 2 * max_tracks:
- *     n_seq * (max_tracks * (12 * max_history + 41) + 16 * cap + 132)
- *   (histories 12 * max_history per track: 0.49 GB of 0.73 GB for 256 sequences x 10 000 tracks x 16 entries), plus
+ *     n_seq * (max_tracks * (12 * max_history + 45) + 16 * cap + 132 + 12 * ceil(max_tracks / 256))
+ *   (histories 12 * max_history per track: 0.49 GB of 0.74 GB for 256 sequences x 10 000 tracks x 16 entries; 4 of the 45
+ *   bytes per track and the last term are the scratch of the packed export's scan: length and ring head per track, a
+ *   32-bit sum and a 64-bit base per block of 256 tracks), plus
  *   16 * 96 * n_seq bytes of pinned host memory.
  *   Returns NULL on failure with the reason in *status_out (optional) and the text in mld_tracks_last_error(NULL).
  *   Destroy the store before its context.
@@ -526,6 +530,17 @@ int mld_tracklets_depths_device(mld_ctx* ctx, int n_seq, int bank_cur, int have_
  *   u / v the float of the stored integer (:237-238).  Entries at or beyond the length are NOT written (fixed stride: no
  *   callee resize, no prefix sum).  Either table may be NULL.
  *
+ * mld_tracks_export_packed_device: the tracks of mld_tracks_export_device (last committed frame, that frame's order)
+ *   without the holes.  offsets_out[s] (required) = n_tracks[s] + 1 int64: offsets[i] = the sum of the stored lengths of
+ *   tracks 0 .. i-1, offsets[n] = the entries of the sequence; len_out[i] of the fixed-stride export is
+ *   offsets[i+1] - offsets[i].  fp_out[s] = capacity[s] x 3 float32: entry e of track i (newest first, (u, v, d)) at
+ *   position offsets[i] + e - bit for bit the concatenation over i of fp[i, :len[i]] of the fixed-stride export, a
+ *   repeated id's history included.  The fp_out table may be NULL (offsets only); with it `capacity` is required,
+ *   capacity[s] >= 0.  Positions >= capacity[s] are not written and nothing at or beyond min(offsets[n], capacity[s]) is
+ *   touched; the offsets are complete all the same, so offsets[n] > capacity[s] tells a truncated sequence.
+ *   capacity[s] = n_tracks[s] * max_history never truncates.  A sequence without tracks needs no arrays and gets nothing
+ *   written; a capacity of 0 needs no fp_out[s].  Any other null array of a sequence with tracks is refused.  Asynchronous, no synchronisation, no host read of device data, nothing allocated per call.
+ *
  * mld_tracks_counts: counts_out = n_seq x 6 int64 of the last committed frame: [0] live tracks, [1] created this frame,
  *   [2] updated this frame, [3] stored features with d >= 0, [4] the other stored features, [5] repeated ids.
  *
@@ -542,6 +557,8 @@ int mld_tracks_begin_device(mld_tracks* tr, const int32_t* const* ids, const int
 int mld_tracks_commit_device(mld_tracks* tr, const float* const* u_new, const float* const* v_new, const float* const* u_old,
                              const float* const* v_old, const float* const* d_cur, const float* const* d_last);
 int mld_tracks_export_device(mld_tracks* tr, float* const* fp_out, int32_t* const* len_out);
+int mld_tracks_export_packed_device(mld_tracks* tr, float* const* fp_out, const int64_t* capacity,
+                                    int64_t* const* offsets_out);
 int mld_tracks_counts(mld_tracks* tr, int64_t* counts_out);
 int mld_tracklets_step_device(mld_ctx* ctx, mld_tracks* tr, int bank_cur, int have_last, const int32_t* const* ids,
                               const float* const* u_new, const float* const* v_new, const float* const* u_old,

@@ -196,6 +196,7 @@ _SIGNATURES = [
     ("mld_tracks_begin_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64), _P(C.c_void_p)]),
     ("mld_tracks_commit_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 6),
     ("mld_tracks_export_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p)]),
+    ("mld_tracks_export_packed_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64), _P(C.c_void_p)]),
     ("mld_tracks_counts", C.c_int, [C.c_void_p, _P(C.c_int64)]),
     ("mld_tracklets_step_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [_P(C.c_void_p)] * 5 +
      [_P(C.c_int64)] + [_P(C.c_void_p)] * 4),

@@ -30,8 +30,25 @@
 //   k_tracks_commit    commit: one thread per track: a new track pops a row, the track claims a slot of the other
 //                      table with atomicCAS, then pushes its entries
 //   k_tracks_export / k_tracks_count   read-only
+//   k_tracks_pack_sums / _scan / _write   read-only: the packed export, tracks back to back with offsets (below)
 // Rows are released before they are taken and never in the same kernel, so max_tracks rows per sequence sustain
 // max_tracks tracks per frame at any churn, and the stack needs no ABA care.
+//
+// The packed export (mld_tracks_export_packed_device) is a segmented exclusive scan of the tracks' lengths followed by
+// a compaction, three kernels over the same flat (sequence, chunk of 256 tracks) blocks, no block ever waiting on
+// another (no look-back, no flags):
+//   k_tracks_pack_sums   block b: the sum of its 256 lengths (wave64 reduction) -> pack_sum[b] (32 bits: at most
+//                        256 * 65535); every track's length and ring head, gathered through its row here, are left in
+//                        pack_meta in track order so that the third pass reads them coalesced
+//   k_tracks_pack_scan   one block per sequence: exclusive scan of the sequence's block sums, kScanWidth at a time with
+//                        a 64-bit carry -> pack_base[b]
+//   k_tracks_pack_write  block b: rescans its 256 lengths (pack_meta) into LDS, writes offsets[i] = pack_base[b] + the local
+//                        prefix (the last block of a sequence adds offsets[n]), then walks its own contiguous output
+//                        range below the capacity with one thread per entry - the owning track by a binary search in
+//                        the LDS prefix, the ring position as k_tracks_export - so that the 12-byte entries leave as
+//                        contiguous runs.
+//   pack_sum / pack_base hold one entry per possible block, n_seq * ceil(max_tracks / 256), pack_meta one 32-bit word
+//   per track (length | head << 16: both are below 65536); allocated at create.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -59,9 +76,15 @@ struct TrSeq {
     const float* u_old;
     const float* v_old;
     const float* d_cur;
-    const float* d_last;
+    union {
+        const float* d_last;
+        int64_t capacity;  // mld_tracks_export_packed_device: entries fp_out holds
+    };
     float* fp_out;
-    int32_t* len_out;
+    union {
+        int32_t* len_out;      // mld_tracks_export_device
+        int64_t* offsets_out;  // mld_tracks_export_packed_device
+    };
     int32_t n;          // tracks of the frame the call works on
     int32_t n_prev;     // tracks of the committed frame (release pass)
     int32_t blk0;       // first block of the sequence in a launch over n (export: over n * max_history)
@@ -82,6 +105,9 @@ struct TrDev {
     int32_t* dup_row;           // [2][n_seq][M]
     unsigned int* cnt;          // [n_seq][4]: new, old, repeated ids, tracks dropped for want of a row (never)
     unsigned long long* feat;   // [n_seq][2]: stored features with d >= 0, the others
+    uint32_t* pack_sum;         // [n_seq * ceil(M / 256)]: packed export, the entries of every block of 256 tracks
+    unsigned long long* pack_base;  // the same blocks: entries of the sequence in front of the block
+    uint32_t* pack_meta;        // [n_seq][M]: packed export, length | head << 16 of every track of the committed frame
     int32_t n_seq, M, H;
     uint32_t cap;
 };
@@ -309,6 +335,112 @@ __global__ __launch_bounds__(kBlock) void k_tracks_count(TrDev T, const TrSeq* _
     }
 }
 
+// ---- the packed export ----
+constexpr int kScanWidth = 256;  // block sums one pass of k_tracks_pack_scan takes (its block size)
+
+
+// Exclusive prefix of one value per thread over the 256 threads of a block; *total = the sum, in every thread.
+template <typename V>
+__device__ __forceinline__ V block_scan_exclusive(V v, V* s_wave, V* total) {
+    const int lane = (int)threadIdx.x & 63, w = (int)threadIdx.x >> 6;
+    V inc = v;
+    for (int off = 1; off < 64; off <<= 1) {
+        const V up = __shfl_up(inc, off);
+        if (lane >= off) inc += up;
+    }
+    if (lane == 63) s_wave[w] = inc;
+    __syncthreads();
+    V before = 0, all = 0;
+    for (int k = 0; k < kBlock / 64; k++) {
+        const V t = s_wave[k];
+        if (k < w) before += t;
+        all += t;
+    }
+    __syncthreads();  // (s_wave is free for the caller's next scan)
+    *total = all;
+    return before + inc - v;
+}
+
+__global__ __launch_bounds__(kBlock) void k_tracks_pack_sums(TrDev T, const TrSeq* __restrict__ desc, int cur) {
+    __shared__ uint32_t s_wave[kBlock / 64];
+    const int s = seq_of_block<false>(desc, T.n_seq, (int)blockIdx.x);
+    const TrSeq& q = desc[s];
+    const int i = ((int)blockIdx.x - q.blk0) * kBlock + (int)threadIdx.x;
+    uint32_t sum = 0;
+    if (i < q.n) {  // (a repeated id that lost has the stored occurrence's row: it exports that history)
+        const size_t base = (size_t)s * T.M;
+        const int row = T.row[((size_t)cur * T.n_seq + s) * T.M + (size_t)i];
+        sum = row >= 0 ? (uint32_t)T.len[base + row] : 0u;
+        const uint32_t head = sum ? (uint32_t)T.head[base + row] : 0u;
+        T.pack_meta[base + i] = sum | (head << 16);  // (max_history <= 65535)
+    }
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t all = 0;
+        for (int k = 0; k < kBlock / 64; k++) all += s_wave[k];
+        T.pack_sum[blockIdx.x] = all;
+    }
+}
+
+__global__ __launch_bounds__(kScanWidth) void k_tracks_pack_scan(TrDev T, const TrSeq* __restrict__ desc) {
+    static_assert(kScanWidth == kBlock, "block_scan_exclusive scans kBlock threads");
+    __shared__ unsigned long long s_wave[kBlock / 64];
+    const TrSeq& q = desc[blockIdx.x];
+    const int nb = (q.n + kBlock - 1) / kBlock;  // (uniform over the block: every thread takes every pass)
+    unsigned long long carry = 0;
+    for (int j0 = 0; j0 < nb; j0 += kScanWidth) {
+        const int j = j0 + (int)threadIdx.x;
+        const unsigned long long v = j < nb ? (unsigned long long)T.pack_sum[q.blk0 + j] : 0ull;
+        unsigned long long all;
+        const unsigned long long before = block_scan_exclusive(v, s_wave, &all);
+        if (j < nb) T.pack_base[q.blk0 + j] = carry + before;
+        carry += all;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_tracks_pack_write(TrDev T, const TrSeq* __restrict__ desc, int cur) {
+    __shared__ uint32_t s_wave[kBlock / 64];
+    __shared__ uint32_t s_off[kBlock + 1];
+    __shared__ int32_t s_row[kBlock], s_head[kBlock];
+    const int s = seq_of_block<false>(desc, T.n_seq, (int)blockIdx.x);
+    const TrSeq& q = desc[s];
+    const int t = (int)threadIdx.x;
+    const int i = ((int)blockIdx.x - q.blk0) * kBlock + t;
+    const size_t base = (size_t)s * T.M;
+    const uint32_t meta = i < q.n ? T.pack_meta[base + i] : 0u;
+    const uint32_t len = meta & 0xffffu;
+    uint32_t total;
+    const uint32_t before = block_scan_exclusive(len, s_wave, &total);
+    const long long first = (long long)T.pack_base[blockIdx.x];  // entries of the sequence in front of this block
+    s_off[t] = before;
+    s_row[t] = len ? T.row[((size_t)cur * T.n_seq + s) * T.M + (size_t)i] : -1;
+    s_head[t] = (int32_t)(meta >> 16);
+    if (t == 0) s_off[kBlock] = total;
+    if (i < q.n) q.offsets_out[i] = first + (long long)before;
+    if (i == q.n - 1) q.offsets_out[q.n] = first + (long long)total;
+    __syncthreads();
+    const long long room = (long long)q.capacity - first;  // entries of this block's range below the capacity
+    if (!q.fp_out || room <= 0) return;
+    const uint32_t limit = room < (long long)total ? (uint32_t)room : total;
+    float* __restrict__ dst0 = q.fp_out + (size_t)first * 3;
+    for (uint32_t e = (uint32_t)t; e < limit; e += kBlock) {
+        int lo = 0, hi = kBlock;  // the last track whose prefix is <= e: tracks without entries in front of it are passed
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (s_off[mid] <= e) lo = mid; else hi = mid;
+        }
+        int p = s_head[lo] + (int)(e - s_off[lo]);
+        if (p >= T.H) p -= T.H;
+        const float* __restrict__ src = T.hist + ((base + s_row[lo]) * (size_t)T.H + p) * 3;
+        float* dst = dst0 + (size_t)e * 3;
+        dst[0] = src[0];
+        dst[1] = src[1];
+        dst[2] = src[2];
+    }
+}
+
 char g_create_error[512] = "";
 
 }  // namespace
@@ -414,6 +546,10 @@ int allocate(mld_tracks* tr) {
     if ((rc = dev_alloc(tr, &d.dup_row, 2 * S * M, true))) return rc;
     if ((rc = dev_alloc(tr, &d.cnt, S * 4, true))) return rc;
     if ((rc = dev_alloc(tr, &d.feat, S * 2, true))) return rc;
+    const size_t pack_blocks = S * ((M + kBlock - 1) / kBlock);
+    if ((rc = dev_alloc(tr, &d.pack_sum, pack_blocks, false))) return rc;
+    if ((rc = dev_alloc(tr, &d.pack_base, pack_blocks, false))) return rc;
+    if ((rc = dev_alloc(tr, &d.pack_meta, S * M, false))) return rc;
     if ((rc = dev_alloc(tr, &tr->own_mask, S * M, true))) return rc;
     if ((rc = dev_alloc(tr, &tr->d_desc, S, true))) return rc;
     tr->gen_bytes = S * sizeof(TrSeq);
@@ -594,6 +730,42 @@ int mld_tracks_export_device(mld_tracks* tr, float* const* fp_out, int32_t* cons
     if (blocks == 0) return MLD_OK;
     if ((rc = upload(tr))) return rc;
     hipLaunchKernelGGL(k_tracks_export, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc, tr->committed);
+    TR_HIP(tr, hipGetLastError());
+    return MLD_OK;
+}
+
+int mld_tracks_export_packed_device(mld_tracks* tr, float* const* fp_out, const int64_t* capacity,
+                                    int64_t* const* offsets_out) {
+    if (!tr) return MLD_ERR_INVALID_ARG;
+    if (!offsets_out) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_export_packed_device: null offsets_out table");
+    if (fp_out && !capacity) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_export_packed_device: fp_out without capacity");
+    const int S = tr->d.n_seq;
+    for (int s = 0; s < S; s++) {
+        if (fp_out && capacity[s] < 0) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_export_packed_device: negative capacity");
+        if (tr->n_committed[(size_t)s] > 0 && !offsets_out[s])
+            return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_export_packed_device: null offsets_out array");
+        if (tr->n_committed[(size_t)s] > 0 && fp_out && !fp_out[s] && capacity[s] > 0)  // (no entries need no array)
+            return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_export_packed_device: null fp_out array");
+    }
+    TR_HIP(tr, hipSetDevice(tr->device));
+    for (int s = 0; s < S; s++) {
+        TrSeq& q = tr->stage[(size_t)s];
+        q = TrSeq{};
+        q.fp_out = fp_out ? fp_out[s] : nullptr;
+        q.capacity = q.fp_out ? capacity[s] : 0;
+        q.offsets_out = offsets_out[s];
+        q.n = tr->n_committed[(size_t)s];
+    }
+    int64_t blocks = 0, blocks_prev = 0;
+    int rc = layout_blocks(tr, 1, &blocks, &blocks_prev);
+    if (rc) return rc;
+    if (blocks == 0) return MLD_OK;
+    if ((rc = upload(tr))) return rc;
+    hipLaunchKernelGGL(k_tracks_pack_sums, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc, tr->committed);
+    TR_HIP(tr, hipGetLastError());
+    hipLaunchKernelGGL(k_tracks_pack_scan, dim3((unsigned)S), dim3(kScanWidth), 0, tr->stream, tr->d, tr->d_desc);
+    TR_HIP(tr, hipGetLastError());
+    hipLaunchKernelGGL(k_tracks_pack_write, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc, tr->committed);
     TR_HIP(tr, hipGetLastError());
     return MLD_OK;
 }

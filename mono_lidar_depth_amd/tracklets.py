@@ -210,6 +210,28 @@ class TrackletStore:
         self._check(self._lib.mld_tracks_export_device(self._tr, self._vp(fp_out), self._vp(len_out)))
         self._keep["export"] = (fp_out, len_out)
 
+    def packed_capacity(self, n_tracks: int) -> int:
+        """Entries an fp_out of export_packed() needs so that a sequence of n_tracks tracks is never truncated."""
+        return int(n_tracks) * self.max_history
+
+    def export_packed(self, fp_out, offsets_out):
+        """The tracks of export() back to back (mld_tracks_export_packed_device).  offsets_out: S int64 CUDA tensors
+        [n_tracks + 1] - track i of sequence s holds entries offsets[i] .. offsets[i + 1] - 1, offsets[n_tracks] is the
+        sequence's total.  fp_out: None (offsets only), or S contiguous float32 CUDA tensors [capacity, 3] ((u, v, d),
+        newest first within a track); entries at or beyond a tensor's capacity are dropped, which the caller sees from
+        offsets[n_tracks] > capacity.  packed_capacity(n_tracks) never truncates."""
+        cap = None
+        if fp_out is not None:
+            for t in fp_out:
+                if not t.is_contiguous():
+                    raise ValueError("fp_out: contiguous tensors")
+            cap = (C.c_int64 * self.S)(*[int(t.numel()) // 3 for t in fp_out])
+        self._check(self._lib.mld_tracks_export_packed_device(self._tr, self._vp(fp_out), cap, self._vp(offsets_out)))
+        # the arrays must outlive the asynchronous launches (the previous call's as well: it may still be queued)
+        now = (list(fp_out) if fp_out is not None else None, list(offsets_out) if offsets_out is not None else None)
+        prev = self._keep.get("export_packed")
+        self._keep["export_packed"] = (prev[1] if prev else None, now)
+
     def counts(self) -> np.ndarray:
         """[S, 6] int64 of the last committed frame, columns COUNT_NAMES.  Synchronises."""
         out = np.zeros((self.S, 6), dtype=np.int64)
