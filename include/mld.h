@@ -626,6 +626,71 @@ int mld_labels_assign_device(mld_labels* lb, const uint8_t* const* label_image_d
                              int32_t* const* votes_out);
 
 /*
+ * Semantic ground planes for a batch — SemanticPlane::CalculateInliersPlane (RansacPlane.cpp:195-274) for n_seq
+ * independent sequences in one call: the plane TrackletDepthModule::process builds from the label image of every frame
+ * (tracklet_depth_module.cpp:269-284, labels 6..9) and hands, un-segmented, to CalculateDepth.  What
+ * mld_estimate_semantic_plane_device does for one slot (four launches, one synchronisation, after the slot's cloud has
+ * been projected) this does for all sequences with four launches and none - and BEFORE the projection: clouds and
+ * images are read where they lie, no slot is involved, and the masks it writes are the mask_dev[s] arrays of
+ * mld_set_clouds_planes_range_device, so that the plane rides in the pixel-map keys.
+ *
+ * mld_semantic_planes_create: an object bound to `ctx` (its stream, its device) for calls of n_seq (1 .. 65536)
+ *   sequences of up to max_points (1 .. 8 388 607) points each.  camera (focal_length, principal_point_x / _y; width and
+ *   height are not read: the bounds are the label image's) and T_cam_lidar are the reference's SemanticPlane::Camera -
+ *   pass the values the context was created with.  All memory is allocated here, none per call:
+ *     device  n_seq * (40 * ceil(max_points / 64) + 48) bytes   (moment sums per 64 points, descriptor, first plane)
+ *     pinned  16 * 32 * n_seq bytes                             (the descriptor ring)
+ *   The sizes are checked before the context is looked at.  Returns NULL on failure with the reason in *status_out
+ *   (optional) and the text in mld_semantic_planes_last_error(NULL).  Destroy the object before its context.
+ *
+ * mld_semantic_planes_estimate_device: tables of n_seq entries.
+ *   pts_dev[s], n[s]    the cloud of sequence s: n[s] records of stride_bytes (16 or 32, x y z first), 4-byte aligned.
+ *                       0 <= n[s] <= max_points (beyond it: MLD_ERR_CAPACITY).
+ *   label_image_dev[s]  rows x cols uint8, row_stride_bytes >= cols between rows, no alignment.  One geometry and one
+ *                       label set for all sequences; ground_labels outside 0 .. 255 never match.
+ *   inlier_threshold    as mld_estimate_semantic_plane.
+ *   result_out_dev      DEVICE array of n_seq records (4-byte aligned).
+ *   mask_out_dev[s]     ceil(n[s] / 32) uint32 words, 4-byte aligned: bit i of word i / 32 = point i is an inlier.  Every
+ *                       word is written, the bits at and beyond n[s] are 0, nothing beyond the last word is touched.
+ *   Per sequence the record and the mask are bit for bit what mld_estimate_semantic_plane_device computes on the same
+ *   cloud (same projection arithmetic, same association of the float moment sums, same eigenvector routine).  Three
+ *   candidates are no failure: the first plane is then the dummy prior (0, 0, 1, 0) (:241-242).
+ *   A sequence with n[s] < 3 or fewer than 3 candidates - the reference's ExceptionPclInvalid (:224-227), which the
+ *   caller of the reference answers with depths of -1 from its catch block (tracklet_depth_module.cpp:338-351) - gets
+ *   status 1, coefficients 0, n_inliers 0 (n_candidates: what was found) and a mask of zeros; the other sequences are
+ *   unaffected and the return code stays MLD_OK.  What to do with such a frame is the caller's business (skip its depths,
+ *   or run it without a plane).  n[s] == 0 needs no cloud, image or mask array and gets its record only.
+ *   Asynchronous on the context's stream: no synchronisation, no host read of device data.  The host tables are consumed
+ *   before the call returns, so a caller may queue frames ahead; the device arrays must stay valid until the work has
+ *   run.  Like a context, the object serves one call at a time.
+ *   The coefficients are wanted on the HOST by mld_set_clouds_planes_range_device: a caller that feeds that entry point
+ *   copies the 32 * n_seq bytes of records back and synchronises once per batch.  That round trip remains; taking the
+ *   coefficients from device memory would be a change inside the context.
+ *   MLD_ERR_INVALID_ARG with a text naming the argument (mld_semantic_planes_last_error; of NULL for a null object) on:
+ *   a null object or table, a null array of a sequence with points, rows or cols < 1, row_stride_bytes < cols, n[s] < 0,
+ *   a stride other than 16 or 32, n_labels < 0 or ground_labels NULL with n_labels > 0, a cloud or mask that is not
+ *   4-byte aligned.
+ */
+typedef struct mld_semantic_plane_result {   /* 32 bytes */
+    float   coeffs[4];      /* plane of the refit, LIDAR frame (RansacPlane.cpp:253,259) */
+    int32_t n_candidates;   /* points whose projection hit a ground label (:198-221) */
+    int32_t n_inliers;      /* points within inlier_threshold of the first fit (:252) */
+    int32_t status;         /* 0 ok, 1 = ExceptionPclInvalid (:224-227) */
+    int32_t reserved;       /* 0 */
+} mld_semantic_plane_result;
+
+typedef struct mld_semantic_planes mld_semantic_planes;
+mld_semantic_planes* mld_semantic_planes_create(mld_ctx* ctx, int n_seq, int64_t max_points, const mld_camera* camera,
+                                                const double T_cam_lidar[12], int* status_out);
+void mld_semantic_planes_destroy(mld_semantic_planes* sp);
+const char* mld_semantic_planes_last_error(const mld_semantic_planes* sp);
+int mld_semantic_planes_estimate_device(mld_semantic_planes* sp, const void* const* pts_dev, const int64_t* n,
+                                        int stride_bytes, const uint8_t* const* label_image_dev, int rows, int cols,
+                                        int row_stride_bytes, const int32_t* ground_labels, int n_labels,
+                                        double inlier_threshold, mld_semantic_plane_result* result_out_dev,
+                                        uint32_t* const* mask_out_dev);
+
+/*
  * Debug / parity getters (host buffers; each synchronises).
  *   mld_get_visible_count           -> _points_cs_image_visible.cols()         (DepthEstimator.cpp:192)
  *   mld_get_visible_image_points    -> getPointsCloudImageCs, 2 x Nvis col-major (:392-394)

@@ -12,7 +12,9 @@ history) is host bookkeeping in the one-frame TrackletDepthModule, kept here in 
 GPU: TrackletStore (mld_tracks_*) decides the new tracks, keeps the histories, drops the dead tracks and exports the
 stored tracks in message order, and TrackletBatch.step runs a whole frame of every sequence with it.  SemanticLabels
 (mld_labels_*) is the node that follows tracklets_depth in the reference's launch files: the label of every track by
-majority vote in a window of a label image (matches_conversion_ros_tool, semantic_labels.cpp:50-72).
+majority vote in a window of a label image (matches_conversion_ros_tool, semantic_labels.cpp:50-72).  SemanticPlanes
+(mld_semantic_planes_*) is the ground plane process() builds from the label image of every frame (:269-284), for all
+sequences of a batch in one call and ahead of the projection.
 """
 from __future__ import annotations
 
@@ -312,6 +314,77 @@ class SemanticLabels:
             pass
 
 
+class SemanticPlanes:
+    """SemanticPlane::CalculateInliersPlane (RansacPlane.cpp:195-274) for S sequences per call (mld_semantic_planes_*,
+    include/mld.h): per sequence the plane of the refit, the candidate and inlier counts, a status (1 = the reference's
+    ExceptionPclInvalid) and the inlier bitmask - bit for bit what DepthEstimator.estimateSemanticPlane gives for that
+    cloud, without a frame slot and before the projection.  Lists of S torch CUDA tensors in and out; asynchronous on
+    the estimator's stream.  Close it before its estimator."""
+
+    def __init__(self, estimator: DepthEstimator, n_seq: int, max_points: int):
+        self._est, self._lib = estimator, estimator._lib
+        self.S, self.max_points = int(n_seq), int(max_points)
+        st = C.c_int(0)
+        cam = estimator._camera.as_struct()
+        T = np.ascontiguousarray(np.asarray(estimator._T, dtype=np.float64).reshape(-1)[:12])
+        self._sp = self._lib.mld_semantic_planes_create(estimator._ctx, self.S, self.max_points, C.byref(cam),
+                                                        T.ctypes.data_as(C.POINTER(C.c_double)), C.byref(st))
+        if not self._sp:
+            raise DepthEstimatorError(st.value, self._lib.mld_semantic_planes_last_error(None).decode())
+        self._keep = None
+
+    @staticmethod
+    def mask_words(n_points: int) -> int:
+        """32-bit words of the inlier mask of a cloud of n_points."""
+        return (int(n_points) + 31) // 32
+
+    def estimate(self, clouds, images, labels, inlier_threshold: float, result_out, masks_out):
+        """clouds: S contiguous float32 CUDA tensors [n, 4] or [n, 8] of one width; images: S uint8 CUDA tensors
+        [rows, cols] of one shape and row stride (unit column stride); labels: the ground labels; result_out: an int32
+        CUDA tensor [S, 8] that receives the records (capi.MldSemanticPlaneResult: coefficients as float bits, then
+        n_candidates, n_inliers, status, 0); masks_out: S int32 CUDA tensors of at least mask_words(n) entries."""
+        S = self.S
+        for name, ts in (("clouds", clouds), ("images", images), ("masks_out", masks_out)):
+            if len(ts) != S:
+                raise ValueError(f"{name}: expected {S} tensors, one per sequence")
+        width = int(clouds[0].shape[1])
+        for s, cl in enumerate(clouds):
+            if cl.dim() != 2 or int(cl.shape[1]) != width or width not in (4, 8) or not cl.is_contiguous() or cl.element_size() != 4:
+                raise ValueError("clouds: contiguous float32 [n, 4] or [n, 8], one width for all sequences")
+            if int(masks_out[s].numel()) * masks_out[s].element_size() < 4 * self.mask_words(cl.shape[0]):
+                raise ValueError(f"sequence {s}: masks_out holds fewer than {self.mask_words(cl.shape[0])} words")
+        rows, cols = (int(x) for x in images[0].shape)
+        stride = int(images[0].stride(0))
+        for im in images:
+            if tuple(im.shape) != (rows, cols) or (rows > 1 and int(im.stride(0)) != stride) or int(im.stride(1)) != 1:
+                raise ValueError("images: one shape and row stride for all sequences, unit column stride")
+        if tuple(result_out.shape) != (S, 8) or result_out.element_size() != 4 or not result_out.is_contiguous():
+            raise ValueError(f"result_out must be a contiguous int32 tensor [{S}, 8]")
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        vp = lambda ts: (C.c_void_p * S)(*[int(t.data_ptr()) for t in ts])  # noqa: E731
+        rc = self._lib.mld_semantic_planes_estimate_device(
+            self._sp, vp(clouds), (C.c_int64 * S)(*[int(c.shape[0]) for c in clouds]), 4 * width, vp(images), rows, cols,
+            max(stride, cols), lab.ctypes.data, int(lab.size), float(inlier_threshold), int(result_out.data_ptr()), vp(masks_out))
+        if rc != capi.MLD_OK:
+            raise DepthEstimatorError(rc, self._lib.mld_semantic_planes_last_error(self._sp).decode())
+        # the arrays must outlive the asynchronous launches (the previous call's as well: it may still be queued)
+        now = (list(clouds), list(images), result_out, list(masks_out))
+        self._keep = (self._keep[1] if self._keep else None, now)
+
+    def close(self):
+        if self._sp:
+            self._lib.mld_semantic_planes_destroy(self._sp)
+            self._sp = None
+        self._keep = None
+
+    def __del__(self):
+        try:
+            if self._est._ctx is not None:  # (the estimator took the stream with it otherwise)
+                self.close()
+        except Exception:
+            pass
+
+
 class TrackletBatch:
     """The tracklet layer for S independent sequences at once (mld_set_clouds_planes_range_device +
     mld_tracklets_depths_device): the estimator's frame slots are two banks of S slots, sequence s keeps its current
@@ -333,6 +406,38 @@ class TrackletBatch:
         self.max_tracks = int(max_tracks)
         self.store: Optional[TrackletStore] = None
         self.semantic_labels: Optional[SemanticLabels] = None
+        self.planes: Optional[SemanticPlanes] = None
+
+    def attach_planes(self, max_points: int = 1 << 19) -> SemanticPlanes:
+        """The semantic ground plane estimator of the S sequences that semantic_planes() runs ahead of a step, for clouds
+        of up to max_points points (default: 128 beams x 4096, 320 KB of scratch per sequence)."""
+        if self.planes is None:
+            self.planes = SemanticPlanes(self.est, self.S, max_points)
+        return self.planes
+
+    def semantic_planes(self, clouds, images, labels=(6, 7, 8, 9), threshold: Optional[float] = None):
+        """The ground planes process() builds from the label images (tracklet_depth_module.cpp:269-284: labels 6..9,
+        threshold ransac_plane_refinement_treshold) for this frame's clouds, ready for prepare_step() / prepare():
+        returns (coeffs float32 [S, 4], masks: S int32 CUDA tensors, status int32 [S], counts int32 [S, 2] =
+        (n_candidates, n_inliers)).  One call on the GPU, then ONE device-to-host copy of 32 * S bytes and one
+        synchronisation per batch: mld_set_clouds_planes_range_device takes the coefficients from the host.  A
+        sequence with status 1 (the reference's ExceptionPclInvalid) has zero coefficients and an empty mask; what to do
+        with its frame is the caller's decision.  attach_planes() first."""
+        import torch
+        if self.planes is None:
+            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.semantic_planes without attach_planes")
+        if threshold is None:
+            threshold = self.est.getParameters().ransac_plane_refinement_treshold
+        dev = clouds[0].device
+        masks = [torch.empty(max(1, SemanticPlanes.mask_words(c.shape[0])), dtype=torch.int32, device=dev) for c in clouds]
+        res = torch.empty((self.S, 8), dtype=torch.int32, device=dev)
+        self.est._after_torch(clouds[0])
+        self.planes.estimate(clouds, images, labels, threshold, res, masks)
+        host = np.empty((self.S, 8), dtype=np.int32)
+        self.est._check(self.est._lib.mld_synchronize(self.est._ctx))
+        host[:] = res.cpu().numpy()
+        coeffs = np.ascontiguousarray(host[:, :4]).view(np.float32)
+        return coeffs, masks, host[:, 6].copy(), host[:, 4:6].copy()
 
     def attach_labels(self) -> SemanticLabels:
         """The label assignment of the S sequences that labels() queues behind a step."""
@@ -440,4 +545,7 @@ class TrackletBatch:
         if self.store is not None:
             self.store.close()
             self.store = None
+        if self.planes is not None:
+            self.planes.close()
+            self.planes = None
         self.est.close()
