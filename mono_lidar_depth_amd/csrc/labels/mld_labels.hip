@@ -8,7 +8,7 @@
 // into TrackletWithOutlierFlag.label.  Here every sequence's tracks are answered by one launch.
 //
 // This translation unit uses the depth path through its public C-ABI only (mld_get_stream); it shares no internals
-// with mld_api.hip or mld_tracks.hip.
+// with mld_api.hip or mld_tracks.hip.  Descriptor ring and object skeleton: ../batch/mld_batch_object.h.
 //
 // Two kernel shapes, chosen per call from the nominal window W x H = 2*(w/2) x 2*(h/2):
 //   k_labels_row   W * H <= 16 (the default roi 5 x 5 counts 4 x 4 pixels).  A block answers 256 tracks, a wavefront 64:
@@ -27,23 +27,18 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
-#include <cstring>
-#include <new>
-#include <string>
 #include <utility>
-#include <vector>
 
-#include "../../../include/mld.h"
+#include "../batch/mld_batch_object.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kGens = 16;            // pinned generations of the descriptor table: the host may run this many calls ahead
 constexpr int kRowTracks = kBlock;   // tracks per block of k_labels_row: one per thread
 constexpr int kWaveTracks = 32;      // tracks per block of k_labels_wave: 8 per wavefront
 constexpr int kNoLabel = -2;         // matches_msg_conversions_ros/convert.hpp:53,97: a track nobody labelled
 
-// One sequence of one call.  Host-made, staged through the pinned ring.
+// One sequence of one call.  Host-made, staged through the descriptor ring (mld_batch::DescRing).
 struct LbSeq {
     const uint8_t* img;
     const float* u;
@@ -53,7 +48,7 @@ struct LbSeq {
     int32_t n;       // tracks
     int32_t blk0;    // first block of the sequence in the launch
 };
-static_assert(sizeof(LbSeq) == 48 && sizeof(LbSeq) % 4 == 0, "the upload kernel moves 32-bit words");
+static_assert(sizeof(LbSeq) == 48, "48 bytes per sequence (DESIGN.md)");
 
 struct LbGeom {
     int32_t rows, cols, stride;
@@ -101,11 +96,6 @@ __device__ __forceinline__ Window window_of(float u, float v, const LbGeom& g) {
         if (win.w == 0 || win.h == 0) win = Window{0, 0, 0, 0};
     }
     return win;
-}
-
-__global__ __launch_bounds__(256) void k_labels_upload(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src_host, int n_words) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n_words) dst[i] = __builtin_nontemporal_load(src_host + i);
 }
 
 // The value of the lane K places further on in this lane's row of 16 (wrapping inside the row).  Every lane of the
@@ -233,113 +223,34 @@ char g_error[512] = "";  // refusals without an object: mld_labels_last_error(NU
 
 }  // namespace
 
-struct mld_labels {
-    mld_ctx* ctx = nullptr;
-    hipStream_t stream = nullptr;
-    int device = 0;
+struct mld_labels : mld_batch::Object {
     int n_seq = 0;
-    LbSeq* d_desc = nullptr;
-    unsigned char* up_base = nullptr;  // pinned: kGens generations of n_seq descriptors
-    size_t gen_bytes = 0;
-    hipEvent_t up_ev[kGens] = {};
-    bool up_busy[kGens] = {};
-    int up_next = 0;
-    std::vector<LbSeq> stage;
-    std::string err;
+    mld_batch::DescRing<LbSeq> ring;
 };
 
 namespace {
 
-int fail(mld_labels* lb, int code, const char* text) {
-    lb->err = text;
-    return code;
-}
-
-#define LB_HIP(lb, expr)                                                                                   \
-    do {                                                                                                   \
-        const hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) {                                                                            \
-            (lb)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                                 \
-            return MLD_ERR_HIP;                                                                            \
-        }                                                                                                  \
-    } while (0)
-
-// The staged descriptors to the device on the context's stream; `lb->stage` may be rewritten as soon as this returns.
-int upload(mld_labels* lb) {
-    const size_t bytes = (size_t)lb->n_seq * sizeof(LbSeq);
-    const int g = lb->up_next;
-    if (lb->up_busy[g]) LB_HIP(lb, hipEventSynchronize(lb->up_ev[g]));  // (only when kGens calls are still queued)
-    unsigned char* pinned = lb->up_base + (size_t)g * lb->gen_bytes;
-    std::memcpy(pinned, lb->stage.data(), bytes);
-    const int words = (int)(bytes / 4);
-    hipLaunchKernelGGL(k_labels_upload, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, lb->stream,
-                       reinterpret_cast<uint32_t*>(lb->d_desc), reinterpret_cast<const uint32_t*>(pinned), words);
-    LB_HIP(lb, hipGetLastError());
-    LB_HIP(lb, hipEventRecord(lb->up_ev[g], lb->stream));
-    lb->up_busy[g] = true;
-    lb->up_next = (g + 1) % kGens;
-    return MLD_OK;
-}
-
-int allocate(mld_labels* lb) {
-    lb->gen_bytes = (size_t)lb->n_seq * sizeof(LbSeq);
-    LB_HIP(lb, hipMalloc((void**)&lb->d_desc, lb->gen_bytes));
-    LB_HIP(lb, hipHostMalloc((void**)&lb->up_base, lb->gen_bytes * kGens, hipHostMallocDefault));
-    for (int g = 0; g < kGens; g++) LB_HIP(lb, hipEventCreateWithFlags(&lb->up_ev[g], hipEventDisableTiming));
-    return MLD_OK;
-}
-
-void release_all(mld_labels* lb) {
-    if (lb->stream) (void)hipStreamSynchronize(lb->stream);
-    if (lb->d_desc) (void)hipFree(lb->d_desc);
-    if (lb->up_base) (void)hipHostFree(lb->up_base);
-    for (int g = 0; g < kGens; g++)
-        if (lb->up_ev[g]) (void)hipEventDestroy(lb->up_ev[g]);
-    delete lb;
-}
+void free_own(mld_labels*) {}  // (the ring is all it has)
 
 }  // namespace
 
 extern "C" {
 
 mld_labels* mld_labels_create(mld_ctx* ctx, int n_seq, int* status_out) {
-    auto refuse = [&](int code, const char* text) -> mld_labels* {
-        std::snprintf(g_error, sizeof(g_error), "%s", text);
-        if (status_out) *status_out = code;
+    auto refusal = [&]() -> const char* {
+        // (the size first: it is refused without a look at the context)
+        if (n_seq < 1 || n_seq > 65536) return "mld_labels_create: n_seq must be in 1 .. 65536";
+        if (!ctx) return "mld_labels_create: null context";
         return nullptr;
     };
-    if (status_out) *status_out = MLD_OK;
-    // (the size first: it is refused without a look at the context)
-    if (n_seq < 1 || n_seq > 65536) return refuse(MLD_ERR_INVALID_ARG, "mld_labels_create: n_seq must be in 1 .. 65536");
-    if (!ctx) return refuse(MLD_ERR_INVALID_ARG, "mld_labels_create: null context");
-    mld_labels* lb = new (std::nothrow) mld_labels();
-    if (!lb) return refuse(MLD_ERR_HIP, "mld_labels_create: out of host memory");
-    lb->ctx = ctx;
-    lb->stream = static_cast<hipStream_t>(mld_get_stream(ctx));
-    hipDevice_t dev = 0;
-    if (hipStreamGetDevice(lb->stream, &dev) != hipSuccess || hipSetDevice((int)dev) != hipSuccess) {
-        delete lb;
-        return refuse(MLD_ERR_HIP, "mld_labels_create: the device of the context's stream is not usable");
-    }
-    lb->device = (int)dev;
-    lb->n_seq = n_seq;
-    lb->stage.assign((size_t)n_seq, LbSeq{});
-    const int rc = allocate(lb);
-    if (rc != MLD_OK) {
-        std::snprintf(g_error, sizeof(g_error), "mld_labels_create: %s", lb->err.c_str());
-        if (status_out) *status_out = rc;
-        lb->stream = nullptr;  // (nothing is in flight that the frees would not wait for)
-        release_all(lb);
-        return nullptr;
-    }
-    return lb;
+    auto init = [&](mld_labels* lb) {
+        lb->n_seq = n_seq;
+        return lb->ring.allocate(lb, n_seq);
+    };
+    return mld_batch::create_object<mld_labels>(g_error, "mld_labels_create", refusal(), ctx, status_out, init, free_own);
 }
 
-void mld_labels_destroy(mld_labels* lb) {
-    if (!lb) return;
-    (void)hipSetDevice(lb->device);
-    release_all(lb);
-}
+void mld_labels_destroy(mld_labels* lb) { mld_batch::destroy_object(lb, free_own); }
 
 const char* mld_labels_last_error(const mld_labels* lb) { return lb ? lb->err.c_str() : g_error; }
 
@@ -373,7 +284,7 @@ int mld_labels_assign_device(mld_labels* lb, const uint8_t* const* label_image_d
     const int per_block = row_shape ? kRowTracks : kWaveTracks;
     int64_t blocks = 0;
     for (int s = 0; s < S; s++) {
-        LbSeq& q = lb->stage[(size_t)s];
+        LbSeq& q = lb->ring.stage[(size_t)s];
         q.img = label_image_dev[s];
         q.u = u[s];
         q.v = v[s];
@@ -385,15 +296,15 @@ int mld_labels_assign_device(mld_labels* lb, const uint8_t* const* label_image_d
         if (blocks > 0x7fffffff) return fail(lb, MLD_ERR_CAPACITY, "mld_labels_assign_device: more than 2^31 blocks in one launch");
     }
     if (blocks == 0) return MLD_OK;
-    LB_HIP(lb, hipSetDevice(lb->device));
-    const int rc = upload(lb);
+    MLD_HIP(lb, hipSetDevice(lb->device));
+    const int rc = lb->ring.upload(lb);
     if (rc) return rc;
     const LbGeom g{rows, cols, row_stride_bytes, hw, hh};
     if (row_shape)
-        hipLaunchKernelGGL(k_labels_row, dim3((unsigned)blocks), dim3(kBlock), 0, lb->stream, lb->d_desc, S, g);
+        hipLaunchKernelGGL(k_labels_row, dim3((unsigned)blocks), dim3(kBlock), 0, lb->stream, lb->ring.d_desc, S, g);
     else
-        hipLaunchKernelGGL(k_labels_wave, dim3((unsigned)blocks), dim3(kBlock), 0, lb->stream, lb->d_desc, S, g);
-    LB_HIP(lb, hipGetLastError());
+        hipLaunchKernelGGL(k_labels_wave, dim3((unsigned)blocks), dim3(kBlock), 0, lb->stream, lb->ring.d_desc, S, g);
+    MLD_HIP(lb, hipGetLastError());
     return MLD_OK;
 }
 

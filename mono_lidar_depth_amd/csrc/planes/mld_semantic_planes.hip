@@ -13,9 +13,9 @@
 //   k_sp_fit<1>      one block per sequence: refit, the record
 //
 // This translation unit uses the depth path through its public C-ABI only (mld_get_stream) and shares no internals with
-// it.  The results are nevertheless bit for bit those of mld_estimate_semantic_plane_device (tests/
-// test_semantic_planes_gpu.py pins that): the helpers below - plane distance, smallest eigenvector of the 3x3 covariance,
-// group reduction - are copies of that path's arithmetic, and the float moment sums keep its association:
+// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h).  The results are nevertheless bit for bit those
+// of mld_estimate_semantic_plane_device (tests/test_semantic_planes_gpu.py pins that): the helpers below - plane
+// distance, smallest eigenvector of the 3x3 covariance, group reduction - are copies of that path's arithmetic, and the float moment sums keep its association:
 //   the nine terms of a member (+0.0f for a non-member) over a GROUP of 64 consecutive points by the xor tree 32, 16, ..., 1;
 //   the group sums, in group order, into 256 interleaved partials (group g -> partial g % 256);
 //   the partials combined in index order.
@@ -25,24 +25,19 @@
 
 #include <cstdint>
 #include <cstdio>
-#include <cstring>
-#include <new>
-#include <string>
-#include <vector>
 
-#include "../../../include/mld.h"
+#include "../batch/mld_batch_object.h"
 
 namespace {
 
 constexpr int kWave = 64;
 constexpr int kBlock = 256;
 constexpr int kPartials = 256;
-constexpr int kGens = 16;            // pinned generations of the descriptor table: the host may run this many calls ahead
 constexpr int kGroupsPerWave = 4;    // consecutive groups a wavefront of the streaming kernels takes (loads issued up front)
 constexpr int kBlockPoints = kBlock * kGroupsPerWave;  // 1024 points = 16 groups per block
 constexpr int64_t kMaxPoints = 8388607;
 
-// One sequence of one call.  Host-made, staged through the pinned ring.
+// One sequence of one call.  Host-made, staged through the descriptor ring (mld_batch::DescRing).
 struct SpSeq {
     const unsigned char* cloud;
     const uint8_t* img;
@@ -50,7 +45,7 @@ struct SpSeq {
     int32_t n;
     int32_t pad_;
 };
-static_assert(sizeof(SpSeq) == 32 && sizeof(SpSeq) % 4 == 0, "the upload kernel moves 32-bit words");
+static_assert(sizeof(SpSeq) == 32, "32 bytes per sequence (DESIGN.md)");
 
 struct LabelSet {
     uint32_t w[8];  // bit l set: label l (0..255) is ground
@@ -159,11 +154,6 @@ __device__ __forceinline__ bool is_candidate(float fx, float fy, float fz, const
         }
     }
     return flag;
-}
-
-__global__ __launch_bounds__(256) void k_sp_upload(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src_host, int n_words) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n_words) dst[i] = __builtin_nontemporal_load(src_host + i);
 }
 
 // Grid (sequence, block of 1024 points).  Wavefront w of block b takes the groups 16 b + 4 w + k, k = 0..3.
@@ -353,78 +343,29 @@ char g_error[512] = "";  // refusals without an object: mld_semantic_planes_last
 
 }  // namespace
 
-struct mld_semantic_planes {
-    mld_ctx* ctx = nullptr;
-    hipStream_t stream = nullptr;
-    int device = 0;
+struct mld_semantic_planes : mld_batch::Object {
     int n_seq = 0;
     int64_t max_points = 0;
     long long groups_per_seq = 0;
     SpCalib calib{};
-    SpSeq* d_desc = nullptr;
     GroupSums* d_groups = nullptr;
-    float* d_first = nullptr;          // the first plane of every sequence
-    unsigned char* up_base = nullptr;  // pinned: kGens generations of n_seq descriptors
-    size_t gen_bytes = 0;
-    hipEvent_t up_ev[kGens] = {};
-    bool up_busy[kGens] = {};
-    int up_next = 0;
-    std::vector<SpSeq> stage;
-    std::string err;
+    float* d_first = nullptr;  // the first plane of every sequence
+    mld_batch::DescRing<SpSeq> ring;
 };
 
 namespace {
 
-int fail(mld_semantic_planes* sp, int code, const char* text) {
-    sp->err = text;
-    return code;
-}
-
-#define SP_HIP(sp, expr)                                                                                   \
-    do {                                                                                                   \
-        const hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) {                                                                            \
-            (sp)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                                 \
-            return MLD_ERR_HIP;                                                                            \
-        }                                                                                                  \
-    } while (0)
-
-// The staged descriptors to the device on the context's stream; `sp->stage` may be rewritten as soon as this returns.
-int upload(mld_semantic_planes* sp) {
-    const size_t bytes = (size_t)sp->n_seq * sizeof(SpSeq);
-    const int g = sp->up_next;
-    if (sp->up_busy[g]) SP_HIP(sp, hipEventSynchronize(sp->up_ev[g]));  // (only when kGens calls are still queued)
-    unsigned char* pinned = sp->up_base + (size_t)g * sp->gen_bytes;
-    std::memcpy(pinned, sp->stage.data(), bytes);
-    const int words = (int)(bytes / 4);
-    hipLaunchKernelGGL(k_sp_upload, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, sp->stream,
-                       reinterpret_cast<uint32_t*>(sp->d_desc), reinterpret_cast<const uint32_t*>(pinned), words);
-    SP_HIP(sp, hipGetLastError());
-    SP_HIP(sp, hipEventRecord(sp->up_ev[g], sp->stream));
-    sp->up_busy[g] = true;
-    sp->up_next = (g + 1) % kGens;
-    return MLD_OK;
-}
-
 int allocate(mld_semantic_planes* sp) {
-    sp->gen_bytes = (size_t)sp->n_seq * sizeof(SpSeq);
-    SP_HIP(sp, hipMalloc((void**)&sp->d_desc, sp->gen_bytes));
-    SP_HIP(sp, hipMalloc((void**)&sp->d_groups, (size_t)sp->n_seq * (size_t)sp->groups_per_seq * sizeof(GroupSums)));
-    SP_HIP(sp, hipMalloc((void**)&sp->d_first, (size_t)sp->n_seq * 4 * sizeof(float)));
-    SP_HIP(sp, hipHostMalloc((void**)&sp->up_base, sp->gen_bytes * kGens, hipHostMallocDefault));
-    for (int g = 0; g < kGens; g++) SP_HIP(sp, hipEventCreateWithFlags(&sp->up_ev[g], hipEventDisableTiming));
+    const int rc = sp->ring.allocate(sp, sp->n_seq);
+    if (rc) return rc;
+    MLD_HIP(sp, hipMalloc((void**)&sp->d_groups, (size_t)sp->n_seq * (size_t)sp->groups_per_seq * sizeof(GroupSums)));
+    MLD_HIP(sp, hipMalloc((void**)&sp->d_first, (size_t)sp->n_seq * 4 * sizeof(float)));
     return MLD_OK;
 }
 
-void release_all(mld_semantic_planes* sp) {
-    if (sp->stream) (void)hipStreamSynchronize(sp->stream);
-    if (sp->d_desc) (void)hipFree(sp->d_desc);
+void free_own(mld_semantic_planes* sp) {
     if (sp->d_groups) (void)hipFree(sp->d_groups);
     if (sp->d_first) (void)hipFree(sp->d_first);
-    if (sp->up_base) (void)hipHostFree(sp->up_base);
-    for (int g = 0; g < kGens; g++)
-        if (sp->up_ev[g]) (void)hipEventDestroy(sp->up_ev[g]);
-    delete sp;
 }
 
 template <int kStride>
@@ -433,14 +374,14 @@ void launch_all(mld_semantic_planes* sp, int chunks, const SpGeom& g, const Labe
     const int S = sp->n_seq;
     const dim3 stream_grid((unsigned)S, (unsigned)chunks), fit_grid((unsigned)S);
     if (chunks > 0)
-        hipLaunchKernelGGL(k_sp_candidates<kStride>, stream_grid, dim3(kBlock), 0, sp->stream, sp->d_desc, sp->calib, g, ls,
+        hipLaunchKernelGGL(k_sp_candidates<kStride>, stream_grid, dim3(kBlock), 0, sp->stream, sp->ring.d_desc, sp->calib, g, ls,
                            sp->d_groups, sp->groups_per_seq);
-    hipLaunchKernelGGL(k_sp_fit<0>, fit_grid, dim3(kPartials), 0, sp->stream, sp->d_desc, sp->d_groups, sp->groups_per_seq,
+    hipLaunchKernelGGL(k_sp_fit<0>, fit_grid, dim3(kPartials), 0, sp->stream, sp->ring.d_desc, sp->d_groups, sp->groups_per_seq,
                        sp->d_first, res);
     if (chunks > 0)
-        hipLaunchKernelGGL(k_sp_select<kStride>, stream_grid, dim3(kBlock), 0, sp->stream, sp->d_desc, sp->d_first, res, thr,
+        hipLaunchKernelGGL(k_sp_select<kStride>, stream_grid, dim3(kBlock), 0, sp->stream, sp->ring.d_desc, sp->d_first, res, thr,
                            sp->d_groups, sp->groups_per_seq);
-    hipLaunchKernelGGL(k_sp_fit<1>, fit_grid, dim3(kPartials), 0, sp->stream, sp->d_desc, sp->d_groups, sp->groups_per_seq,
+    hipLaunchKernelGGL(k_sp_fit<1>, fit_grid, dim3(kPartials), 0, sp->stream, sp->ring.d_desc, sp->d_groups, sp->groups_per_seq,
                        sp->d_first, res);
 }
 
@@ -450,53 +391,30 @@ extern "C" {
 
 mld_semantic_planes* mld_semantic_planes_create(mld_ctx* ctx, int n_seq, int64_t max_points, const mld_camera* camera,
                                                 const double T_cam_lidar[12], int* status_out) {
-    auto refuse = [&](int code, const char* text) -> mld_semantic_planes* {
-        std::snprintf(g_error, sizeof(g_error), "%s", text);
-        if (status_out) *status_out = code;
+    auto refusal = [&]() -> const char* {
+        // (the sizes first: they are refused without a look at the context)
+        if (n_seq < 1 || n_seq > 65536) return "mld_semantic_planes_create: n_seq must be in 1 .. 65536";
+        if (max_points < 1 || max_points > kMaxPoints) return "mld_semantic_planes_create: max_points must be in 1 .. 8388607";
+        if (!ctx) return "mld_semantic_planes_create: null context";
+        if (!camera) return "mld_semantic_planes_create: null camera";
+        if (!T_cam_lidar) return "mld_semantic_planes_create: null T_cam_lidar";
         return nullptr;
     };
-    if (status_out) *status_out = MLD_OK;
-    // (the sizes first: they are refused without a look at the context)
-    if (n_seq < 1 || n_seq > 65536) return refuse(MLD_ERR_INVALID_ARG, "mld_semantic_planes_create: n_seq must be in 1 .. 65536");
-    if (max_points < 1 || max_points > kMaxPoints)
-        return refuse(MLD_ERR_INVALID_ARG, "mld_semantic_planes_create: max_points must be in 1 .. 8388607");
-    if (!ctx) return refuse(MLD_ERR_INVALID_ARG, "mld_semantic_planes_create: null context");
-    if (!camera) return refuse(MLD_ERR_INVALID_ARG, "mld_semantic_planes_create: null camera");
-    if (!T_cam_lidar) return refuse(MLD_ERR_INVALID_ARG, "mld_semantic_planes_create: null T_cam_lidar");
-    mld_semantic_planes* sp = new (std::nothrow) mld_semantic_planes();
-    if (!sp) return refuse(MLD_ERR_HIP, "mld_semantic_planes_create: out of host memory");
-    sp->ctx = ctx;
-    sp->stream = static_cast<hipStream_t>(mld_get_stream(ctx));
-    hipDevice_t dev = 0;
-    if (hipStreamGetDevice(sp->stream, &dev) != hipSuccess || hipSetDevice((int)dev) != hipSuccess) {
-        delete sp;
-        return refuse(MLD_ERR_HIP, "mld_semantic_planes_create: the device of the context's stream is not usable");
-    }
-    sp->device = (int)dev;
-    sp->n_seq = n_seq;
-    sp->max_points = max_points;
-    sp->groups_per_seq = (long long)((max_points + kWave - 1) / kWave);
-    for (int t = 0; t < 12; t++) sp->calib.T[t] = T_cam_lidar[t];
-    sp->calib.f = camera->focal_length;
-    sp->calib.cu = camera->principal_point_x;
-    sp->calib.cv = camera->principal_point_y;
-    sp->stage.assign((size_t)n_seq, SpSeq{});
-    const int rc = allocate(sp);
-    if (rc != MLD_OK) {
-        std::snprintf(g_error, sizeof(g_error), "mld_semantic_planes_create: %s", sp->err.c_str());
-        if (status_out) *status_out = rc;
-        sp->stream = nullptr;  // (nothing is in flight that the frees would not wait for)
-        release_all(sp);
-        return nullptr;
-    }
-    return sp;
+    auto init = [&](mld_semantic_planes* sp) {
+        sp->n_seq = n_seq;
+        sp->max_points = max_points;
+        sp->groups_per_seq = (long long)((max_points + kWave - 1) / kWave);
+        for (int t = 0; t < 12; t++) sp->calib.T[t] = T_cam_lidar[t];
+        sp->calib.f = camera->focal_length;
+        sp->calib.cu = camera->principal_point_x;
+        sp->calib.cv = camera->principal_point_y;
+        return allocate(sp);
+    };
+    return mld_batch::create_object<mld_semantic_planes>(g_error, "mld_semantic_planes_create", refusal(), ctx, status_out, init,
+                                                         free_own);
 }
 
-void mld_semantic_planes_destroy(mld_semantic_planes* sp) {
-    if (!sp) return;
-    (void)hipSetDevice(sp->device);
-    release_all(sp);
-}
+void mld_semantic_planes_destroy(mld_semantic_planes* sp) { mld_batch::destroy_object(sp, free_own); }
 
 const char* mld_semantic_planes_last_error(const mld_semantic_planes* sp) { return sp ? sp->err.c_str() : g_error; }
 
@@ -536,7 +454,7 @@ int mld_semantic_planes_estimate_device(mld_semantic_planes* sp, const void* con
     }
 #undef SP_REFUSE
     for (int s = 0; s < S; s++) {
-        SpSeq& q = sp->stage[(size_t)s];
+        SpSeq& q = sp->ring.stage[(size_t)s];
         q.cloud = static_cast<const unsigned char*>(pts_dev[s]);
         q.img = label_image_dev[s];
         q.mask = mask_out_dev[s];
@@ -546,8 +464,8 @@ int mld_semantic_planes_estimate_device(mld_semantic_planes* sp, const void* con
     LabelSet ls{};
     for (int i = 0; i < n_labels; i++)
         if (ground_labels[i] >= 0 && ground_labels[i] < 256) ls.w[ground_labels[i] >> 5] |= 1u << (ground_labels[i] & 31);
-    SP_HIP(sp, hipSetDevice(sp->device));
-    const int rc = upload(sp);
+    MLD_HIP(sp, hipSetDevice(sp->device));
+    const int rc = sp->ring.upload(sp);
     if (rc) return rc;
     const SpGeom g{rows, cols, row_stride_bytes};
     const int chunks = (int)((longest + kBlockPoints - 1) / kBlockPoints);  // (<= 8192)
@@ -555,7 +473,7 @@ int mld_semantic_planes_estimate_device(mld_semantic_planes* sp, const void* con
         launch_all<16>(sp, chunks, g, ls, inlier_threshold, result_out_dev);
     else
         launch_all<32>(sp, chunks, g, ls, inlier_threshold, result_out_dev);
-    SP_HIP(sp, hipGetLastError());
+    MLD_HIP(sp, hipGetLastError());
     return MLD_OK;
 }
 

@@ -7,7 +7,8 @@
 // map of every sequence lives in GPU memory and those four steps are kernels over all sequences at once.
 //
 // This translation unit uses the depth path through its public C-ABI only (mld_get_stream, mld_last_error,
-// mld_tracklets_depths_device); it shares no internals with mld_api.hip.
+// mld_tracklets_depths_device); it shares no internals with mld_api.hip.  Descriptor ring and object skeleton:
+// ../batch/mld_batch_object.h.
 //
 // Data, per sequence (everything allocated in mld_tracks_create):
 //   table[2][cap]      open-addressed id tables, cap = power of two >= 2 * max_tracks, linear probing.  A slot is
@@ -53,21 +54,18 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <new>
 #include <string>
 #include <vector>
 
-#include "../../../include/mld.h"
+#include "../batch/mld_batch_object.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kGens = 16;  // pinned generations of the descriptor table: the host may run this many uploads ahead
 constexpr unsigned long long kOccupied = 1ull << 63;
 
-// One sequence of one call.  Host-made, staged through the pinned ring, read by every kernel of the call.
+// One sequence of one call.  Host-made, staged through the descriptor ring (mld_batch::DescRing), read by every kernel
+// of the call.
 struct TrSeq {
     const int32_t* ids;
     uint8_t* is_new;
@@ -90,7 +88,7 @@ struct TrSeq {
     int32_t blk0;       // first block of the sequence in a launch over n (export: over n * max_history)
     int32_t blk0_prev;  // the same for the release pass (at least one block per sequence)
 };
-static_assert(sizeof(TrSeq) == 96 && sizeof(TrSeq) % 4 == 0, "the upload kernel moves 32-bit words");
+static_assert(sizeof(TrSeq) == 96, "96 bytes per sequence (DESIGN.md)");
 
 struct TrDev {
     unsigned long long* table;  // [2][n_seq][cap]
@@ -137,11 +135,6 @@ __device__ __forceinline__ int seq_of_block(const TrSeq* __restrict__ desc, int 
 __device__ __forceinline__ void wave_count(unsigned int* dst, bool pred) {
     const unsigned long long m = __ballot(pred);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(dst, (unsigned int)__popcll(m));
-}
-
-__global__ __launch_bounds__(256) void k_tracks_upload(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src_host, int n_words) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n_words) dst[i] = __builtin_nontemporal_load(src_host + i);
 }
 
 __global__ __launch_bounds__(256) void k_tracks_init(TrDev T) {
@@ -445,19 +438,11 @@ char g_create_error[512] = "";
 
 }  // namespace
 
-struct mld_tracks {
-    mld_ctx* ctx = nullptr;
-    hipStream_t stream = nullptr;
-    int device = 0;
+struct mld_tracks : mld_batch::Object {
     TrDev d{};
     std::vector<void*> allocs;
     uint8_t* own_mask = nullptr;  // [n_seq][M]: the masks of a begin without is_new_out
-    TrSeq* d_desc = nullptr;
-    unsigned char* up_base = nullptr;  // pinned: kGens generations of n_seq descriptors
-    size_t gen_bytes = 0;
-    hipEvent_t up_ev[kGens] = {};
-    bool up_busy[kGens] = {};
-    int up_next = 0;
+    mld_batch::DescRing<TrSeq> ring;
     // host-side frame state: everything a call needs is known when it is issued, nothing is read back
     int committed = 0;      // the table / per-track arrays of the last committed frame
     bool begun = false;
@@ -465,49 +450,16 @@ struct mld_tracks {
     std::vector<int32_t> n_committed, n_pending;
     std::vector<const int32_t*> ids_pending;
     std::vector<uint8_t*> mask_pending;
-    std::vector<TrSeq> stage;
     std::vector<const uint8_t*> mask_table;  // mld_tracklets_step_device
-    std::string err;
 };
 
 namespace {
-
-int fail(mld_tracks* tr, int code, const char* text) {
-    tr->err = text;
-    return code;
-}
-
-#define TR_HIP(tr, expr)                                                                                   \
-    do {                                                                                                   \
-        const hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) {                                                                            \
-            (tr)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                                 \
-            return MLD_ERR_HIP;                                                                            \
-        }                                                                                                  \
-    } while (0)
-
-// The staged descriptors to the device on the store's stream; `tr->stage` may be rewritten as soon as this returns.
-int upload(mld_tracks* tr) {
-    const size_t bytes = (size_t)tr->d.n_seq * sizeof(TrSeq);
-    const int g = tr->up_next;
-    if (tr->up_busy[g]) TR_HIP(tr, hipEventSynchronize(tr->up_ev[g]));
-    unsigned char* pinned = tr->up_base + (size_t)g * tr->gen_bytes;
-    std::memcpy(pinned, tr->stage.data(), bytes);
-    const int words = (int)(bytes / 4);
-    hipLaunchKernelGGL(k_tracks_upload, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, tr->stream,
-                       reinterpret_cast<uint32_t*>(tr->d_desc), reinterpret_cast<const uint32_t*>(pinned), words);
-    TR_HIP(tr, hipGetLastError());
-    TR_HIP(tr, hipEventRecord(tr->up_ev[g], tr->stream));
-    tr->up_busy[g] = true;
-    tr->up_next = (g + 1) % kGens;
-    return MLD_OK;
-}
 
 // Block prefixes of the staged descriptors: per sequence ceil(n * per_track / kBlock) blocks, and for the release pass
 // ceil(n_prev / kBlock) but at least one.  Returns the two totals.
 int layout_blocks(mld_tracks* tr, int per_track, int64_t* total, int64_t* total_prev) {
     int64_t b = 0, bp = 0;
-    for (TrSeq& q : tr->stage) {
+    for (TrSeq& q : tr->ring.stage) {
         q.blk0 = (int32_t)b;
         q.blk0_prev = (int32_t)bp;
         b += ((int64_t)q.n * per_track + kBlock - 1) / kBlock;
@@ -523,9 +475,9 @@ template <typename T>
 int dev_alloc(mld_tracks* tr, T** p, size_t count, bool zero) {
     void* q = nullptr;
     const size_t bytes = std::max<size_t>(count * sizeof(T), 4);
-    TR_HIP(tr, hipMalloc(&q, bytes));
+    MLD_HIP(tr, hipMalloc(&q, bytes));
     tr->allocs.push_back(q);
-    if (zero) TR_HIP(tr, hipMemsetAsync(q, 0, bytes, tr->stream));
+    if (zero) MLD_HIP(tr, hipMemsetAsync(q, 0, bytes, tr->stream));
     *p = static_cast<T*>(q);
     return MLD_OK;
 }
@@ -551,23 +503,17 @@ int allocate(mld_tracks* tr) {
     if ((rc = dev_alloc(tr, &d.pack_base, pack_blocks, false))) return rc;
     if ((rc = dev_alloc(tr, &d.pack_meta, S * M, false))) return rc;
     if ((rc = dev_alloc(tr, &tr->own_mask, S * M, true))) return rc;
-    if ((rc = dev_alloc(tr, &tr->d_desc, S, true))) return rc;
-    tr->gen_bytes = S * sizeof(TrSeq);
-    TR_HIP(tr, hipHostMalloc((void**)&tr->up_base, tr->gen_bytes * kGens, hipHostMallocDefault));
-    for (int g = 0; g < kGens; g++) TR_HIP(tr, hipEventCreateWithFlags(&tr->up_ev[g], hipEventDisableTiming));
+    if ((rc = tr->ring.allocate(tr, d.n_seq))) return rc;
+    // (the table starts as zeros, like the rest of the store's memory)
+    MLD_HIP(tr, hipMemsetAsync(tr->ring.d_desc, 0, tr->ring.gen_bytes, tr->stream));
     const size_t total = std::max(S * M, S);
     hipLaunchKernelGGL(k_tracks_init, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, tr->stream, d);
-    TR_HIP(tr, hipGetLastError());
+    MLD_HIP(tr, hipGetLastError());
     return MLD_OK;
 }
 
-void release_all(mld_tracks* tr) {
-    if (tr->stream) (void)hipStreamSynchronize(tr->stream);
+void free_own(mld_tracks* tr) {
     for (void* p : tr->allocs) (void)hipFree(p);
-    if (tr->up_base) (void)hipHostFree(tr->up_base);
-    for (int g = 0; g < kGens; g++)
-        if (tr->up_ev[g]) (void)hipEventDestroy(tr->up_ev[g]);
-    delete tr;
 }
 
 }  // namespace
@@ -575,58 +521,32 @@ void release_all(mld_tracks* tr) {
 extern "C" {
 
 mld_tracks* mld_tracks_create(mld_ctx* ctx, int n_seq, int64_t max_tracks, int max_history, int* status_out) {
-    auto refuse = [&](int code, const char* text) -> mld_tracks* {
-        std::snprintf(g_create_error, sizeof(g_create_error), "%s", text);
-        if (status_out) *status_out = code;
+    auto refusal = [&]() -> const char* {
+        // (the sizes first: they are refused without a look at the context)
+        if (n_seq < 1 || n_seq > 65536) return "mld_tracks_create: n_seq must be in 1 .. 65536";
+        if (max_tracks < 1 || max_tracks > (1 << 24)) return "mld_tracks_create: max_tracks must be in 1 .. 16777216";
+        if (max_history < 2 || max_history > 65535) return "mld_tracks_create: max_history must be in 2 .. 65535";
+        if (!ctx) return "mld_tracks_create: null context";
         return nullptr;
     };
-    if (status_out) *status_out = MLD_OK;
-    // (the sizes first: they are refused without a look at the context)
-    if (n_seq < 1 || n_seq > 65536) return refuse(MLD_ERR_INVALID_ARG, "mld_tracks_create: n_seq must be in 1 .. 65536");
-    if (max_tracks < 1 || max_tracks > (1 << 24))
-        return refuse(MLD_ERR_INVALID_ARG, "mld_tracks_create: max_tracks must be in 1 .. 16777216");
-    if (max_history < 2 || max_history > 65535)
-        return refuse(MLD_ERR_INVALID_ARG, "mld_tracks_create: max_history must be in 2 .. 65535");
-    if (!ctx) return refuse(MLD_ERR_INVALID_ARG, "mld_tracks_create: null context");
-    mld_tracks* tr = new (std::nothrow) mld_tracks();
-    if (!tr) return refuse(MLD_ERR_HIP, "mld_tracks_create: out of host memory");
-    tr->ctx = ctx;
-    // the store lives on the context's stream and on that stream's device
-    tr->stream = static_cast<hipStream_t>(mld_get_stream(ctx));
-    hipDevice_t dev = 0;
-    if (hipStreamGetDevice(tr->stream, &dev) != hipSuccess || hipSetDevice((int)dev) != hipSuccess) {
-        delete tr;
-        return refuse(MLD_ERR_HIP, "mld_tracks_create: the device of the context's stream is not usable");
-    }
-    tr->device = (int)dev;
-    tr->d.n_seq = n_seq;
-    tr->d.M = (int32_t)max_tracks;
-    tr->d.H = max_history;
-    uint32_t cap = 2;
-    while (cap < 2u * (uint32_t)max_tracks) cap <<= 1;
-    tr->d.cap = cap;
-    tr->n_committed.assign((size_t)n_seq, 0);
-    tr->n_pending.assign((size_t)n_seq, 0);
-    tr->ids_pending.assign((size_t)n_seq, nullptr);
-    tr->mask_pending.assign((size_t)n_seq, nullptr);
-    tr->mask_table.assign((size_t)n_seq, nullptr);
-    tr->stage.assign((size_t)n_seq, TrSeq{});
-    const int rc = allocate(tr);
-    if (rc != MLD_OK) {
-        std::snprintf(g_create_error, sizeof(g_create_error), "mld_tracks_create: %s", tr->err.c_str());
-        if (status_out) *status_out = rc;
-        tr->stream = nullptr;  // (nothing of the store is in flight that the frees would not wait for)
-        release_all(tr);
-        return nullptr;
-    }
-    return tr;
+    auto init = [&](mld_tracks* tr) {
+        tr->d.n_seq = n_seq;
+        tr->d.M = (int32_t)max_tracks;
+        tr->d.H = max_history;
+        uint32_t cap = 2;
+        while (cap < 2u * (uint32_t)max_tracks) cap <<= 1;
+        tr->d.cap = cap;
+        tr->n_committed.assign((size_t)n_seq, 0);
+        tr->n_pending.assign((size_t)n_seq, 0);
+        tr->ids_pending.assign((size_t)n_seq, nullptr);
+        tr->mask_pending.assign((size_t)n_seq, nullptr);
+        tr->mask_table.assign((size_t)n_seq, nullptr);
+        return allocate(tr);
+    };
+    return mld_batch::create_object<mld_tracks>(g_create_error, "mld_tracks_create", refusal(), ctx, status_out, init, free_own);
 }
 
-void mld_tracks_destroy(mld_tracks* tr) {
-    if (!tr) return;
-    (void)hipSetDevice(tr->device);
-    release_all(tr);
-}
+void mld_tracks_destroy(mld_tracks* tr) { mld_batch::destroy_object(tr, free_own); }
 
 const char* mld_tracks_last_error(const mld_tracks* tr) { return tr ? tr->err.c_str() : g_create_error; }
 
@@ -640,9 +560,9 @@ int mld_tracks_begin_device(mld_tracks* tr, const int32_t* const* ids, const int
         if (n_tracks[s] > 0 && (!ids[s] || (is_new_out && !is_new_out[s])))
             return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_begin_device: null array");
     }
-    TR_HIP(tr, hipSetDevice(tr->device));
+    MLD_HIP(tr, hipSetDevice(tr->device));
     for (int s = 0; s < S; s++) {
-        TrSeq& q = tr->stage[(size_t)s];
+        TrSeq& q = tr->ring.stage[(size_t)s];
         q = TrSeq{};
         q.ids = ids[s];
         q.is_new = is_new_out ? is_new_out[s] : tr->own_mask + (size_t)s * tr->d.M;
@@ -659,10 +579,10 @@ int mld_tracks_begin_device(mld_tracks* tr, const int32_t* const* ids, const int
     int rc = layout_blocks(tr, 1, &blocks, &blocks_prev);
     if (rc) return rc;
     if (blocks == 0) return MLD_OK;
-    if ((rc = upload(tr))) return rc;
-    hipLaunchKernelGGL(k_tracks_lookup, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc, tr->committed,
+    if ((rc = tr->ring.upload(tr))) return rc;
+    hipLaunchKernelGGL(k_tracks_lookup, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed,
                        tr->epoch);
-    TR_HIP(tr, hipGetLastError());
+    MLD_HIP(tr, hipGetLastError());
     return MLD_OK;
 }
 
@@ -676,9 +596,9 @@ int mld_tracks_commit_device(mld_tracks* tr, const float* const* u_new, const fl
     for (int s = 0; s < S; s++)
         if (tr->n_pending[(size_t)s] > 0 && (!u_new[s] || !v_new[s] || !u_old[s] || !v_old[s] || !d_cur[s] || !d_last[s]))
             return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_commit_device: null array");
-    TR_HIP(tr, hipSetDevice(tr->device));
+    MLD_HIP(tr, hipSetDevice(tr->device));
     for (int s = 0; s < S; s++) {
-        TrSeq& q = tr->stage[(size_t)s];
+        TrSeq& q = tr->ring.stage[(size_t)s];
         q = TrSeq{};
         q.ids = tr->ids_pending[(size_t)s];
         q.is_new = tr->mask_pending[(size_t)s];
@@ -694,14 +614,14 @@ int mld_tracks_commit_device(mld_tracks* tr, const float* const* u_new, const fl
     int64_t blocks = 0, blocks_prev = 0;
     int rc = layout_blocks(tr, 1, &blocks, &blocks_prev);
     if (rc) return rc;
-    if ((rc = upload(tr))) return rc;
-    hipLaunchKernelGGL(k_tracks_release, dim3((unsigned)blocks_prev), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc,
+    if ((rc = tr->ring.upload(tr))) return rc;
+    hipLaunchKernelGGL(k_tracks_release, dim3((unsigned)blocks_prev), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc,
                        tr->committed, tr->epoch);
-    TR_HIP(tr, hipGetLastError());
+    MLD_HIP(tr, hipGetLastError());
     if (blocks > 0) {
-        hipLaunchKernelGGL(k_tracks_commit, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc,
+        hipLaunchKernelGGL(k_tracks_commit, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc,
                            1 - tr->committed);
-        TR_HIP(tr, hipGetLastError());
+        MLD_HIP(tr, hipGetLastError());
     }
     tr->committed = 1 - tr->committed;
     tr->n_committed = tr->n_pending;
@@ -716,9 +636,9 @@ int mld_tracks_export_device(mld_tracks* tr, float* const* fp_out, int32_t* cons
     for (int s = 0; s < S; s++)
         if (tr->n_committed[(size_t)s] > 0 && ((fp_out && !fp_out[s]) || (len_out && !len_out[s])))
             return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_export_device: null array");
-    TR_HIP(tr, hipSetDevice(tr->device));
+    MLD_HIP(tr, hipSetDevice(tr->device));
     for (int s = 0; s < S; s++) {
-        TrSeq& q = tr->stage[(size_t)s];
+        TrSeq& q = tr->ring.stage[(size_t)s];
         q = TrSeq{};
         q.fp_out = fp_out ? fp_out[s] : nullptr;
         q.len_out = len_out ? len_out[s] : nullptr;
@@ -728,9 +648,9 @@ int mld_tracks_export_device(mld_tracks* tr, float* const* fp_out, int32_t* cons
     int rc = layout_blocks(tr, tr->d.H, &blocks, &blocks_prev);
     if (rc) return rc;
     if (blocks == 0) return MLD_OK;
-    if ((rc = upload(tr))) return rc;
-    hipLaunchKernelGGL(k_tracks_export, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc, tr->committed);
-    TR_HIP(tr, hipGetLastError());
+    if ((rc = tr->ring.upload(tr))) return rc;
+    hipLaunchKernelGGL(k_tracks_export, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed);
+    MLD_HIP(tr, hipGetLastError());
     return MLD_OK;
 }
 
@@ -747,9 +667,9 @@ int mld_tracks_export_packed_device(mld_tracks* tr, float* const* fp_out, const 
         if (tr->n_committed[(size_t)s] > 0 && fp_out && !fp_out[s] && capacity[s] > 0)  // (no entries need no array)
             return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_export_packed_device: null fp_out array");
     }
-    TR_HIP(tr, hipSetDevice(tr->device));
+    MLD_HIP(tr, hipSetDevice(tr->device));
     for (int s = 0; s < S; s++) {
-        TrSeq& q = tr->stage[(size_t)s];
+        TrSeq& q = tr->ring.stage[(size_t)s];
         q = TrSeq{};
         q.fp_out = fp_out ? fp_out[s] : nullptr;
         q.capacity = q.fp_out ? capacity[s] : 0;
@@ -760,13 +680,13 @@ int mld_tracks_export_packed_device(mld_tracks* tr, float* const* fp_out, const 
     int rc = layout_blocks(tr, 1, &blocks, &blocks_prev);
     if (rc) return rc;
     if (blocks == 0) return MLD_OK;
-    if ((rc = upload(tr))) return rc;
-    hipLaunchKernelGGL(k_tracks_pack_sums, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc, tr->committed);
-    TR_HIP(tr, hipGetLastError());
-    hipLaunchKernelGGL(k_tracks_pack_scan, dim3((unsigned)S), dim3(kScanWidth), 0, tr->stream, tr->d, tr->d_desc);
-    TR_HIP(tr, hipGetLastError());
-    hipLaunchKernelGGL(k_tracks_pack_write, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc, tr->committed);
-    TR_HIP(tr, hipGetLastError());
+    if ((rc = tr->ring.upload(tr))) return rc;
+    hipLaunchKernelGGL(k_tracks_pack_sums, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed);
+    MLD_HIP(tr, hipGetLastError());
+    hipLaunchKernelGGL(k_tracks_pack_scan, dim3((unsigned)S), dim3(kScanWidth), 0, tr->stream, tr->d, tr->ring.d_desc);
+    MLD_HIP(tr, hipGetLastError());
+    hipLaunchKernelGGL(k_tracks_pack_write, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed);
+    MLD_HIP(tr, hipGetLastError());
     return MLD_OK;
 }
 
@@ -774,26 +694,26 @@ int mld_tracks_counts(mld_tracks* tr, int64_t* counts_out) {
     if (!tr) return MLD_ERR_INVALID_ARG;
     if (!counts_out) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_counts: null output");
     const int S = tr->d.n_seq;
-    TR_HIP(tr, hipSetDevice(tr->device));
+    MLD_HIP(tr, hipSetDevice(tr->device));
     for (int s = 0; s < S; s++) {
-        TrSeq& q = tr->stage[(size_t)s];
+        TrSeq& q = tr->ring.stage[(size_t)s];
         q = TrSeq{};
         q.n = tr->n_committed[(size_t)s];
     }
     int64_t blocks = 0, blocks_prev = 0;
     int rc = layout_blocks(tr, 1, &blocks, &blocks_prev);
     if (rc) return rc;
-    TR_HIP(tr, hipMemsetAsync(tr->d.feat, 0, (size_t)S * 2 * sizeof(unsigned long long), tr->stream));
+    MLD_HIP(tr, hipMemsetAsync(tr->d.feat, 0, (size_t)S * 2 * sizeof(unsigned long long), tr->stream));
     if (blocks > 0) {
-        if ((rc = upload(tr))) return rc;
-        hipLaunchKernelGGL(k_tracks_count, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->d_desc, tr->committed);
-        TR_HIP(tr, hipGetLastError());
+        if ((rc = tr->ring.upload(tr))) return rc;
+        hipLaunchKernelGGL(k_tracks_count, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed);
+        MLD_HIP(tr, hipGetLastError());
     }
     std::vector<unsigned int> cnt((size_t)S * 4);
     std::vector<unsigned long long> feat((size_t)S * 2);
-    TR_HIP(tr, hipMemcpyAsync(cnt.data(), tr->d.cnt, cnt.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, tr->stream));
-    TR_HIP(tr, hipMemcpyAsync(feat.data(), tr->d.feat, feat.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, tr->stream));
-    TR_HIP(tr, hipStreamSynchronize(tr->stream));
+    MLD_HIP(tr, hipMemcpyAsync(cnt.data(), tr->d.cnt, cnt.size() * sizeof(unsigned int), hipMemcpyDeviceToHost, tr->stream));
+    MLD_HIP(tr, hipMemcpyAsync(feat.data(), tr->d.feat, feat.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, tr->stream));
+    MLD_HIP(tr, hipStreamSynchronize(tr->stream));
     for (int s = 0; s < S; s++) {
         int64_t* c = counts_out + (size_t)s * 6;
         c[1] = cnt[(size_t)s * 4 + 0];

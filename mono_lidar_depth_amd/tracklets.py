@@ -163,7 +163,64 @@ class TrackletDepthModule:
         return list(self._tracklet_map[track_id])
 
 
-class TrackletStore:
+class _BatchObject:
+    """What TrackletStore, SemanticLabels and SemanticPlanes share: an object of the C-ABI (mld_<_NAME>_create /
+    _destroy / _last_error) on an estimator's context, its handle in the attribute named _HANDLE, and the tensors of
+    the calls that may still be queued."""
+
+    _NAME = _HANDLE = ""
+
+    def _create(self, estimator: DepthEstimator, *args):
+        self._est, self._lib = estimator, estimator._lib
+        st = C.c_int(0)
+        handle = getattr(self._lib, f"mld_{self._NAME}_create")(estimator._ctx, *args, C.byref(st))
+        setattr(self, self._HANDLE, handle)
+        if not handle:
+            raise DepthEstimatorError(st.value, self._last_error(None))
+        self._keep = {}
+
+    def _last_error(self, handle) -> str:
+        return getattr(self._lib, f"mld_{self._NAME}_last_error")(handle).decode()
+
+    def _check(self, rc: int):
+        if rc != capi.MLD_OK:
+            raise DepthEstimatorError(rc, self._last_error(getattr(self, self._HANDLE)))
+
+    def _ptrs(self, ts):
+        """The table of the S device pointers of `ts` (an entry None: NULL)."""
+        return (C.c_void_p * self.S)(*[int(t.data_ptr()) if t is not None else None for t in ts])
+
+    def _hold(self, now, call=None):
+        """The arrays must outlive the asynchronous launches (the previous call's as well: it may still be queued)."""
+        prev = self._keep.get(call)
+        self._keep[call] = (prev[1] if prev else None, now)
+
+    @staticmethod
+    def _image_geometry(images):
+        """(rows, cols, row stride) that all label images of a call must share."""
+        rows, cols = (int(x) for x in images[0].shape)
+        stride = int(images[0].stride(0))
+        for im in images:
+            if tuple(im.shape) != (rows, cols) or (rows > 1 and int(im.stride(0)) != stride) or int(im.stride(1)) != 1:
+                raise ValueError("images: one shape and row stride for all sequences, unit column stride")
+        return rows, cols, stride
+
+    def close(self):
+        handle = getattr(self, self._HANDLE)
+        if handle:
+            getattr(self._lib, f"mld_{self._NAME}_destroy")(handle)
+            setattr(self, self._HANDLE, None)
+        self._keep = {}
+
+    def __del__(self):
+        try:
+            if self._est._ctx is not None:  # (the estimator took the stream with it otherwise)
+                self.close()
+        except Exception:
+            pass
+
+
+class TrackletStore(_BatchObject):
     """`_trackletMap` of S independent sequences in GPU memory (mld_tracks_*, include/mld.h): begin = which ids are new
     (ExractNewTrackletFrames :23-61), commit = SaveFeatureDepths + TidyUpTracklets (:119-193), export =
     convert_tracklets_to_matches_msg (:209-259).  Histories hold at most `max_history` entries per track (the
@@ -171,26 +228,18 @@ class TrackletStore:
     only counts() synchronises.  Close the store before its estimator."""
 
     COUNT_NAMES = ("live", "new", "old", "features_ok", "features_failed", "duplicates")
+    _NAME, _HANDLE = "tracks", "_tr"
 
     def __init__(self, estimator: DepthEstimator, n_seq: int, max_tracks: int, max_history: int):
-        self._est, self._lib = estimator, estimator._lib
         self.S, self.max_tracks, self.max_history = int(n_seq), int(max_tracks), int(max_history)
-        st = C.c_int(0)
-        self._tr = self._lib.mld_tracks_create(estimator._ctx, self.S, self.max_tracks, self.max_history, C.byref(st))
-        if not self._tr:
-            raise DepthEstimatorError(st.value, self._lib.mld_tracks_last_error(None).decode())
-        self._keep = {}
-
-    def _check(self, rc: int):
-        if rc != capi.MLD_OK:
-            raise DepthEstimatorError(rc, self._lib.mld_tracks_last_error(self._tr).decode())
+        self._create(estimator, self.S, self.max_tracks, self.max_history)
 
     def _vp(self, ts):
         if ts is None:
             return None
         if len(ts) != self.S:
             raise ValueError(f"expected {self.S} tensors, one per sequence")
-        return (C.c_void_p * self.S)(*[int(t.data_ptr()) for t in ts])
+        return self._ptrs(ts)
 
     def begin(self, ids, is_new_out=None):
         """ids: S int32 CUDA tensors; is_new_out: S uint8 CUDA tensors of the same lengths, or None (masks kept in
@@ -229,10 +278,8 @@ class TrackletStore:
                     raise ValueError("fp_out: contiguous tensors")
             cap = (C.c_int64 * self.S)(*[int(t.numel()) // 3 for t in fp_out])
         self._check(self._lib.mld_tracks_export_packed_device(self._tr, self._vp(fp_out), cap, self._vp(offsets_out)))
-        # the arrays must outlive the asynchronous launches (the previous call's as well: it may still be queued)
-        now = (list(fp_out) if fp_out is not None else None, list(offsets_out) if offsets_out is not None else None)
-        prev = self._keep.get("export_packed")
-        self._keep["export_packed"] = (prev[1] if prev else None, now)
+        self._hold((list(fp_out) if fp_out is not None else None, list(offsets_out) if offsets_out is not None else None),
+                   "export_packed")
 
     def counts(self) -> np.ndarray:
         """[S, 6] int64 of the last committed frame, columns COUNT_NAMES.  Synchronises."""
@@ -240,35 +287,18 @@ class TrackletStore:
         self._check(self._lib.mld_tracks_counts(self._tr, out.ctypes.data_as(C.POINTER(C.c_int64))))
         return out
 
-    def close(self):
-        if self._tr:
-            self._lib.mld_tracks_destroy(self._tr)
-            self._tr = None
-        self._keep = {}
 
-    def __del__(self):
-        try:
-            if self._est._ctx is not None:  # (the estimator took the stream with it otherwise)
-                self.close()
-        except Exception:
-            pass
-
-
-class SemanticLabels:
+class SemanticLabels(_BatchObject):
     """assignLabels (matches_conversion_ros_tool/src/semantic_labels/semantic_labels.cpp:50-72) for S sequences per call
     (mld_labels_*, include/mld.h - the window arithmetic and the three defined cases are stated there).  Lists of S
     torch CUDA tensors in and out; asynchronous on the estimator's stream.  Close it before its estimator."""
 
     NO_LABEL = -2
+    _NAME, _HANDLE = "labels", "_lb"
 
     def __init__(self, estimator: DepthEstimator, n_seq: int):
-        self._est, self._lib = estimator, estimator._lib
         self.S = int(n_seq)
-        st = C.c_int(0)
-        self._lb = self._lib.mld_labels_create(estimator._ctx, self.S, C.byref(st))
-        if not self._lb:
-            raise DepthEstimatorError(st.value, self._lib.mld_labels_last_error(None).decode())
-        self._keep = None
+        self._create(estimator, self.S)
 
     def assign(self, images, roi, u, v, label_out, votes_out=None):
         """images: S uint8 CUDA tensors [rows, cols] of one shape and row stride (unit column stride); roi: (width,
@@ -279,59 +309,34 @@ class SemanticLabels:
         for name, ts in (("images", images), ("u", u), ("v", v), ("label_out", label_out), ("votes_out", votes_out)):
             if ts is not None and len(ts) != S:
                 raise ValueError(f"{name}: expected {S} tensors, one per sequence")
-        rows, cols = (int(x) for x in images[0].shape)
-        stride = int(images[0].stride(0))
-        for im in images:
-            if tuple(im.shape) != (rows, cols) or (rows > 1 and int(im.stride(0)) != stride) or int(im.stride(1)) != 1:
-                raise ValueError("images: one shape and row stride for all sequences, unit column stride")
+        rows, cols, stride = self._image_geometry(images)
         for s in range(S):
             n = int(u[s].shape[0])
             if int(v[s].shape[0]) != n or int(label_out[s].shape[0]) != n:
                 raise ValueError(f"sequence {s}: u, v and label_out differ in length")
             if votes_out is not None and votes_out[s] is not None and tuple(votes_out[s].shape) != (n, 2):
                 raise ValueError(f"sequence {s}: votes_out must be [{n}, 2]")
-        vp = lambda ts: (C.c_void_p * S)(*[int(t.data_ptr()) if t is not None else None for t in ts])  # noqa: E731
-        rc = self._lib.mld_labels_assign_device(self._lb, vp(images), rows, cols, max(stride, cols), int(roi[0]), int(roi[1]),
-                                                vp(u), vp(v), (C.c_int64 * S)(*[int(t.shape[0]) for t in u]), vp(label_out),
-                                                vp(votes_out) if votes_out is not None else None)
-        if rc != capi.MLD_OK:
-            raise DepthEstimatorError(rc, self._lib.mld_labels_last_error(self._lb).decode())
-        # the arrays must outlive the asynchronous launch (the previous call's as well: it may still be queued)
-        now = (list(images), list(u), list(v), list(label_out), list(votes_out) if votes_out is not None else None)
-        self._keep = (self._keep[1] if self._keep else None, now)
-
-    def close(self):
-        if self._lb:
-            self._lib.mld_labels_destroy(self._lb)
-            self._lb = None
-        self._keep = None
-
-    def __del__(self):
-        try:
-            if self._est._ctx is not None:  # (the estimator took the stream with it otherwise)
-                self.close()
-        except Exception:
-            pass
+        vp = self._ptrs
+        self._check(self._lib.mld_labels_assign_device(
+            self._lb, vp(images), rows, cols, max(stride, cols), int(roi[0]), int(roi[1]), vp(u), vp(v),
+            (C.c_int64 * S)(*[int(t.shape[0]) for t in u]), vp(label_out), vp(votes_out) if votes_out is not None else None))
+        self._hold((list(images), list(u), list(v), list(label_out), list(votes_out) if votes_out is not None else None))
 
 
-class SemanticPlanes:
+class SemanticPlanes(_BatchObject):
     """SemanticPlane::CalculateInliersPlane (RansacPlane.cpp:195-274) for S sequences per call (mld_semantic_planes_*,
     include/mld.h): per sequence the plane of the refit, the candidate and inlier counts, a status (1 = the reference's
     ExceptionPclInvalid) and the inlier bitmask - bit for bit what DepthEstimator.estimateSemanticPlane gives for that
     cloud, without a frame slot and before the projection.  Lists of S torch CUDA tensors in and out; asynchronous on
     the estimator's stream.  Close it before its estimator."""
 
+    _NAME, _HANDLE = "semantic_planes", "_sp"
+
     def __init__(self, estimator: DepthEstimator, n_seq: int, max_points: int):
-        self._est, self._lib = estimator, estimator._lib
         self.S, self.max_points = int(n_seq), int(max_points)
-        st = C.c_int(0)
         cam = estimator._camera.as_struct()
         T = np.ascontiguousarray(np.asarray(estimator._T, dtype=np.float64).reshape(-1)[:12])
-        self._sp = self._lib.mld_semantic_planes_create(estimator._ctx, self.S, self.max_points, C.byref(cam),
-                                                        T.ctypes.data_as(C.POINTER(C.c_double)), C.byref(st))
-        if not self._sp:
-            raise DepthEstimatorError(st.value, self._lib.mld_semantic_planes_last_error(None).decode())
-        self._keep = None
+        self._create(estimator, self.S, self.max_points, C.byref(cam), T.ctypes.data_as(C.POINTER(C.c_double)))
 
     @staticmethod
     def mask_words(n_points: int) -> int:
@@ -353,36 +358,15 @@ class SemanticPlanes:
                 raise ValueError("clouds: contiguous float32 [n, 4] or [n, 8], one width for all sequences")
             if int(masks_out[s].numel()) * masks_out[s].element_size() < 4 * self.mask_words(cl.shape[0]):
                 raise ValueError(f"sequence {s}: masks_out holds fewer than {self.mask_words(cl.shape[0])} words")
-        rows, cols = (int(x) for x in images[0].shape)
-        stride = int(images[0].stride(0))
-        for im in images:
-            if tuple(im.shape) != (rows, cols) or (rows > 1 and int(im.stride(0)) != stride) or int(im.stride(1)) != 1:
-                raise ValueError("images: one shape and row stride for all sequences, unit column stride")
+        rows, cols, stride = self._image_geometry(images)
         if tuple(result_out.shape) != (S, 8) or result_out.element_size() != 4 or not result_out.is_contiguous():
             raise ValueError(f"result_out must be a contiguous int32 tensor [{S}, 8]")
         lab = np.ascontiguousarray(labels, dtype=np.int32)
-        vp = lambda ts: (C.c_void_p * S)(*[int(t.data_ptr()) for t in ts])  # noqa: E731
-        rc = self._lib.mld_semantic_planes_estimate_device(
+        vp = self._ptrs
+        self._check(self._lib.mld_semantic_planes_estimate_device(
             self._sp, vp(clouds), (C.c_int64 * S)(*[int(c.shape[0]) for c in clouds]), 4 * width, vp(images), rows, cols,
-            max(stride, cols), lab.ctypes.data, int(lab.size), float(inlier_threshold), int(result_out.data_ptr()), vp(masks_out))
-        if rc != capi.MLD_OK:
-            raise DepthEstimatorError(rc, self._lib.mld_semantic_planes_last_error(self._sp).decode())
-        # the arrays must outlive the asynchronous launches (the previous call's as well: it may still be queued)
-        now = (list(clouds), list(images), result_out, list(masks_out))
-        self._keep = (self._keep[1] if self._keep else None, now)
-
-    def close(self):
-        if self._sp:
-            self._lib.mld_semantic_planes_destroy(self._sp)
-            self._sp = None
-        self._keep = None
-
-    def __del__(self):
-        try:
-            if self._est._ctx is not None:  # (the estimator took the stream with it otherwise)
-                self.close()
-        except Exception:
-            pass
+            max(stride, cols), lab.ctypes.data, int(lab.size), float(inlier_threshold), int(result_out.data_ptr()), vp(masks_out)))
+        self._hold((list(clouds), list(images), result_out, list(masks_out)))
 
 
 class TrackletBatch:

@@ -76,8 +76,12 @@ def test_the_labels_are_a_translation_unit_of_their_own():
     csrc = ROOT / "mono_lidar_depth_amd" / "csrc"
     assert (csrc / "labels" / "mld_labels.hip").is_file()
     text = (csrc / "labels" / "mld_labels.hip").read_text()
-    assert '#include "mld_' not in text and "mld_device.h" not in text and "mld_diag.h" not in text
-    assert re.findall(r'#include\s+"([^"]+)"', text) == ["../../../include/mld.h"]
+    # public header only: through the shared header of the batch objects, which itself includes nothing else of the project
+    assert re.findall(r'#include\s+"([^"]+)"', text) == ["../batch/mld_batch_object.h"]
+    shared = (csrc / "batch" / "mld_batch_object.h").read_text()
+    assert re.findall(r'#include\s+"([^"]+)"', shared) == ["../../../include/mld.h"]
+    for src in (text, shared):
+        assert '#include "mld_' not in src and "mld_device.h" not in src and "mld_diag.h" not in src
     mk = (csrc / "Makefile").read_text()
     link_lines = [ln for ln in mk.splitlines() if "-shared" in ln]
     assert len(link_lines) == 2 and all("$(LABELS)" in ln and "$(TRACKS)" in ln for ln in link_lines)

@@ -233,7 +233,50 @@ def test_calls_queued_through_one_set_of_host_tables(est):
     sl.close()
 
 
-SCANNERS = (synth.Scanner(64, 1024, 2.0, -24.9), synth.VLP16)  # the first two of tests/test_tracklets_step_gpu.py
+def test_calls_queued_past_the_last_generation_of_the_descriptor_ring(est):
+    """35 calls (twice the 16 pinned generations of the descriptor ring and three more) with no synchronisation in
+    between, through ONE set of host pointer tables rewritten after every call: every generation's event is waited for
+    and recorded again, and every call's labels and votes equal the restatement.  33 tracks cross a wavefront, one
+    sequence is empty; (5, 5) takes the row kernel, (6, 4) the wavefront kernel, (0, 0) has no pixel in any window."""
+    import torch
+    dev = torch.device("cuda:0")
+    S, ns, rows, cols, calls = 3, (33, 0, 2), 9, 11, 2 * 16 + 3
+    rois = [(5, 5), (6, 4), (0, 0)]
+    rng = np.random.default_rng(1635)
+    lib = capi.load()
+    sl = SemanticLabels(est, S)
+    t_img, t_u, t_v, t_lab, t_vot = ((C.c_void_p * S)() for _ in range(5))
+    t_n = (C.c_int64 * S)()
+    keep, want = [], []
+    for call in range(calls):
+        imgs = [make_image(rng, rows, cols, 5) for _ in range(S)]
+        feats = [make_features(rng, rows, cols, n, call) for n in ns]
+        d_imgs = [device_image(im, 11, dev) for im in imgs]
+        d_u = [torch.from_numpy(np.ascontiguousarray(f[:, 0])).to(dev) for f in feats]
+        d_v = [torch.from_numpy(np.ascontiguousarray(f[:, 1])).to(dev) for f in feats]
+        lab, vot = outputs(ns, dev)
+        keep.append((d_imgs, d_u, d_v, lab, vot))
+        want.append([assign_labels(imgs[s], rois[call % 3], feats[s][:, 0], feats[s][:, 1]) for s in range(S)])
+    torch.cuda.synchronize()
+    for call in range(calls):
+        d_imgs, d_u, d_v, lab, vot = keep[call]
+        roi = rois[call % 3]
+        for s in range(S):
+            t_img[s], t_u[s], t_v[s] = d_imgs[s].data_ptr(), d_u[s].data_ptr(), d_v[s].data_ptr()
+            t_lab[s], t_vot[s], t_n[s] = lab[s].data_ptr(), vot[s].data_ptr(), ns[s]
+        rc = lib.mld_labels_assign_device(sl._lb, t_img, rows, cols, 11, roi[0], roi[1], t_u, t_v, t_n, t_lab, t_vot)
+        assert rc == capi.MLD_OK, lib.mld_labels_last_error(sl._lb).decode()
+        for s in range(S):
+            t_img[s] = t_u[s] = t_v[s] = t_lab[s] = t_vot[s] = None
+            t_n[s] = 0
+    est.synchronize()
+    for call in range(calls):
+        check(ns, want[call], keep[call][3], keep[call][4], "all")
+    assert sum(int((w[0] != NO_LABEL).sum()) for per in want for w in per) > 100
+    sl.close()
+
+
+SCANNERS =(synth.Scanner(64, 1024, 2.0, -24.9), synth.VLP16)  # the first two of tests/test_tracklets_step_gpu.py
 N_TRACKS = (500, 257)
 H = 6
 

@@ -396,6 +396,48 @@ def test_two_calls_queued_through_one_set_of_host_tables(est):
     sp.close()
 
 
+def test_calls_queued_past_the_last_generation_of_the_descriptor_ring(est):
+    """35 calls (twice the 16 pinned generations of the descriptor ring and three more) with no synchronisation in
+    between, through ONE set of host tables rewritten after every call, each call with its own result tensor and
+    guarded masks: every generation's event is waited for and recorded again, and every call equals the oracle."""
+    import torch
+    dev = torch.device("cuda:0")
+    lib = capi.load()
+    S, calls, sizes = 2, 2 * 16 + 3, (3, 63, 64, 65, 255, 257)
+    sp = SemanticPlanes(est, S, 257)
+    t_pts, t_img, t_mask = ((C.c_void_p * S)() for _ in range(3))
+    t_n = (C.c_int64 * S)()
+    lab = (C.c_int32 * 4)(*LABELS)
+    d_cloud = {n: torch.from_numpy(case(n)[0]).to(dev) for n in sizes}
+    d_img = torch.from_numpy(case(sizes[0])[1]).to(dev)  # (every case is a sub-cloud of one frame: one image)
+    assert all(np.array_equal(case(n)[1], case(sizes[0])[1]) for n in sizes)
+    keep = []
+    for k in range(calls):
+        pick = (sizes[k % 6], sizes[(k + 1) % 6])
+        bufs, views = mask_buffers(pick, dev)
+        keep.append((pick, bufs, views, torch.full((S, 8), -1, dtype=torch.int32, device=dev)))
+    torch.cuda.synchronize()
+    for pick, bufs, views, res in keep:
+        for s in range(S):
+            t_pts[s], t_img[s], t_mask[s], t_n[s] = d_cloud[pick[s]].data_ptr(), d_img.data_ptr(), views[s].data_ptr(), pick[s]
+        rc = lib.mld_semantic_planes_estimate_device(sp._sp, t_pts, t_n, 16, t_img, synth.KITTI_H, synth.KITTI_W, synth.KITTI_W,
+                                                     C.addressof(lab), 4, THR, res.data_ptr(), t_mask)
+        assert rc == capi.MLD_OK, lib.mld_semantic_planes_last_error(sp._sp).decode()
+        for s in range(S):
+            t_pts[s] = t_img[s] = t_mask[s] = None
+            t_n[s] = 0
+    est.synchronize()
+    for k, (pick, bufs, views, res) in enumerate(keep):
+        r = res.cpu().numpy()
+        for s in range(S):
+            w = (pick[s] + 31) // 32
+            whole = bufs[s].cpu().numpy()
+            got = (r[s, :4].copy().view(np.float32), int(r[s, 4]), int(r[s, 5]), int(r[s, 6]), whole[:w].view(np.uint32),
+                   bool((whole[w:] == GUARD).all()))
+            check(got, case(pick[s])[2], f"call {k}, n={pick[s]}")
+    sp.close()
+
+
 def test_tracklet_batch_with_its_own_planes_equals_the_oracle_fed_batch():
     """Two sequences, two frames: TrackletBatch.run with the planes of semantic_planes() against a second batch fed the
     oracle's coefficients and inlier masks - depths and types identical, and the road fallback did answer features.

@@ -73,7 +73,12 @@ def test_the_store_is_a_translation_unit_of_its_own():
     csrc = ROOT / "mono_lidar_depth_amd" / "csrc"
     assert (csrc / "tracks" / "mld_tracks.hip").is_file()
     text = (csrc / "tracks" / "mld_tracks.hip").read_text()
-    assert '#include "mld_' not in text and "mld_device.h" not in text  # public header only
+    # public header only: through the shared header of the batch objects, which itself includes nothing else of the project
+    assert re.findall(r'#include\s+"([^"]+)"', text) == ["../batch/mld_batch_object.h"]
+    shared = (csrc / "batch" / "mld_batch_object.h").read_text()
+    assert re.findall(r'#include\s+"([^"]+)"', shared) == ["../../../include/mld.h"]
+    for src in (text, shared):
+        assert '#include "mld_' not in src and "mld_device.h" not in src and "mld_diag.h" not in src
     mk = (csrc / "Makefile").read_text()
     link_lines = [ln for ln in mk.splitlines() if "-shared" in ln]
     assert len(link_lines) == 2 and all("$(TRACKS)" in ln for ln in link_lines)

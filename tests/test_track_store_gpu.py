@@ -410,6 +410,57 @@ def test_frames_enqueued_ahead_equal_frames_run_one_by_one():
     feeder.close()
 
 
+def test_frames_enqueued_past_the_last_generation_of_the_descriptor_ring():
+    """20 frames begun and committed (40 descriptor uploads: twice the 16 pinned generations of the ring and more) with
+    no synchronisation, through ONE set of host tables overwritten after every call, then one export and the counts:
+    every generation's event is waited for and recorded again, and the masks of every frame, the histories and the
+    counts equal the restatement.  33 tracks cross a wavefront; the second sequence is empty on every third frame."""
+    import torch
+    S, M, H, frames = 3, 40, 4, 20
+    rng = np.random.default_rng(41)
+    h = Harness(S, M, H, seed=41)
+    plan, prev, next_id = [], [np.zeros(0, np.int32)] * S, [0, 0, 0]
+    for f in range(frames):
+        ids = []
+        for s in range(S):
+            i, next_id[s] = churn(rng, prev[s], (33, 7 * (f % 3), 1 + f % 2)[s], 0.3, next_id[s])
+            ids.append(i)
+        plan.append((ids,) + h.upload(ids))
+        prev = ids
+    lib = capi.load()
+    tr = h.store._tr
+    tab = [(C.c_void_p * S)() for _ in range(8)]
+    nt = (C.c_int64 * S)()
+    for ids, host, t_ids, t_new, t_feat in plan:
+        for s in range(S):
+            tab[0][s], tab[1][s], nt[s] = t_ids[s].data_ptr(), t_new[s].data_ptr(), len(ids[s])
+            for k in range(6):
+                tab[2 + k][s] = t_feat[k][s].data_ptr()
+        assert lib.mld_tracks_begin_device(tr, tab[0], nt, tab[1]) == 0
+        for s in range(S):  # the host tables are consumed when the call returns
+            tab[0][s], tab[1][s], nt[s] = None, None, 0
+        assert lib.mld_tracks_commit_device(tr, *tab[2:8]) == 0
+        for k in range(6):
+            for s in range(S):
+                tab[2 + k][s] = None
+    ns = [len(i) for i in plan[-1][0]]
+    fp = [torch.full((n, H, 3), float(SENTINEL), dtype=torch.float32, device=h.dev) for n in ns]
+    ln = [torch.full((n,), -9, dtype=torch.int32, device=h.dev) for n in ns]
+    torch.cuda.synchronize()
+    h.store.export(fp, ln)
+    counts = h.store.counts()  # (synchronises)
+    ref = [Restatement(H) for _ in range(S)]
+    for ids, host, t_ids, t_new, t_feat in plan:
+        for s in range(S):
+            assert np.array_equal(t_new[s].cpu().numpy(), ref[s].begin(ids[s])), s
+            ref[s].commit(ids[s], *host[s])
+    for s in range(S):
+        e_len, e_fp = ref[s].export()
+        assert np.array_equal(ln[s].cpu().numpy(), e_len) and np.array_equal(bits(fp[s].cpu().numpy()), bits(e_fp)), s
+        assert counts[s].tolist() == ref[s].counts, s
+    h.close()
+
+
 def test_capacity_and_call_order_are_checked():
     import torch
     from mono_lidar_depth_amd import DepthEstimatorError
