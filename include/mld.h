@@ -691,6 +691,70 @@ int mld_semantic_planes_estimate_device(mld_semantic_planes* sp, const void* con
                                         uint32_t* const* mask_out_dev);
 
 /*
+ * RANSAC ground planes for a batch — RansacPlane::CalculateInliersPlane (RansacPlane.cpp:41-140) for n_seq independent
+ * sequences in one call: the plane of a frame that comes WITHOUT a label image, which DepthEstimator::setInputCloud
+ * estimates by default (DepthEstimator.cpp:275-283).  The twin of mld_semantic_planes: what mld_estimate_ground_plane does
+ * for one slot (after the slot's cloud has been projected, ending in a synchronisation) this does for all sequences with
+ * up to three launches and no synchronisation - and BEFORE the projection: clouds are read where they lie, no slot is
+ * involved (either bank of a two-bank slot layout is served alike), and the masks it writes are the mask_dev[s] arrays
+ * of mld_set_clouds_planes_range_device.
+ *
+ * mld_ransac_planes_create: an object bound to `ctx` (its stream, its device) for calls of n_seq (1 .. 65536) sequences
+ *   of up to max_points (1 .. 8 388 607) points each.  `params` is copied; of it only the fields the estimator reads are
+ *   used: ransac_plane_distance_treshold, ransac_plane_min_z / _max_z (the z pass-through is on when min_z > -1001, as
+ *   for mld_estimate_ground_plane), ransac_plane_max_iterations (0 .. 2^31 - 2), ransac_plane_probability,
+ *   ransac_plane_use_refinement, ransac_plane_refinement_treshold.  All memory is allocated here, none per call:
+ *     device  n_seq * (8 * ceil(max_points / 64) + 4 * ceil(max_points / 1024) + 28) bytes
+ *             (pass-through: candidate mask per 64 points, candidate count per 1024 points; descriptor)
+ *     pinned  16 * 24 * n_seq bytes   (the descriptor ring)
+ *   max_points bounds that scratch and nothing else: there is no size of cloud at which a call takes another, slower or
+ *   synchronising, path.  The sizes are checked before the context is looked at, then the context, then params.  Returns
+ *   NULL on failure with the reason in *status_out (optional) and the text in mld_ransac_planes_last_error(NULL).
+ *   Destroy the object before its context.
+ *
+ * mld_ransac_planes_estimate_device: HOST tables of n_seq entries.
+ *   pts_dev[s], n[s]    the cloud of sequence s: n[s] records of stride_bytes (16 or 32, x y z first), 4-byte aligned.
+ *                       0 <= n[s] <= max_points (beyond it: MLD_ERR_CAPACITY).
+ *   seeds[s]            fixes the random draws of sequence s (the reference's pcl::RandomSample is time-seeded).
+ *   result_out_dev      DEVICE array of n_seq records (4-byte aligned).
+ *   mask_out_dev[s]     ceil(n[s] / 32) uint32 words, 4-byte aligned: bit i of word i / 32 = point i is an inlier.  Every
+ *                       word is written, the bits at and beyond n[s] are 0, nothing beyond the last word is touched.
+ *   Parity contract: per sequence the record and the mask are bit for bit what mld_estimate_ground_plane leaves on a slot
+ *   that holds that cloud, with that seed - coefficients, the inlier set as mld_get_ground_plane_inliers lists it, and
+ *   `iterations` as mld_calculate_depth_frame_estimate reports it (mld_plane_result.iterations).  Two properties of that
+ *   path are kept with it: the inliers come from the (at most 6000) sampled points only, and a cloud in which no draw
+ *   gives a plane within 10 degrees of the z axis adopts its first draw with 0 inliers (status 0).
+ *   A sequence with n[s] < 3, fewer than three candidates of the pass-through or no model at all (every draw degenerate,
+ *   e.g. a cloud of NaN) - GroundPlane::ExceptionPclInvalid - gets status 1, coefficients 0, n_inliers 0, iterations 0
+ *   (n_candidates: what was found) and a mask of zeros; the other sequences are unaffected and the return code stays
+ *   MLD_OK.  What to do with such a frame is the caller's business.  n[s] == 0 needs no cloud or mask array and gets its
+ *   record only.
+ *   Asynchronous on the context's stream: no synchronisation, no host read of device data.  The host tables are consumed
+ *   before the call returns, so a caller may queue frames ahead; the device arrays must stay valid until the work has
+ *   run.  Like a context, the object serves one call at a time.  As for mld_semantic_planes, a caller that feeds
+ *   mld_set_clouds_planes_range_device copies the 32 * n_seq bytes of records back and synchronises once per batch.
+ *   MLD_ERR_INVALID_ARG with a text naming the argument (mld_ransac_planes_last_error; of NULL for a null object) on: a
+ *   null object or table, a null array of a sequence with points, n[s] < 0, a stride other than 16 or 32, a cloud or
+ *   mask that is not 4-byte aligned.
+ */
+typedef struct mld_ransac_plane_result {   /* 32 bytes */
+    float   coeffs[4];     /* LIDAR frame; what mld_estimate_ground_plane returns */
+    int32_t n_inliers;     /* set bits of the mask */
+    int32_t iterations;    /* iterations PCL's stopping rule counted (mld_plane_result.iterations) */
+    int32_t status;        /* 0 ok, 1 = GroundPlane::ExceptionPclInvalid */
+    int32_t n_candidates;  /* points that passed the z pass-through (n when it is off) */
+} mld_ransac_plane_result;
+
+typedef struct mld_ransac_planes mld_ransac_planes;
+mld_ransac_planes* mld_ransac_planes_create(mld_ctx* ctx, int n_seq, int64_t max_points, const mld_params* params,
+                                            int* status_out);
+void mld_ransac_planes_destroy(mld_ransac_planes* rp);
+const char* mld_ransac_planes_last_error(const mld_ransac_planes* rp);
+int mld_ransac_planes_estimate_device(mld_ransac_planes* rp, const void* const* pts_dev, const int64_t* n, int stride_bytes,
+                                      const uint32_t* seeds, mld_ransac_plane_result* result_out_dev,
+                                      uint32_t* const* mask_out_dev);
+
+/*
  * Debug / parity getters (host buffers; each synchronises).
  *   mld_get_visible_count           -> _points_cs_image_visible.cols()         (DepthEstimator.cpp:192)
  *   mld_get_visible_image_points    -> getPointsCloudImageCs, 2 x Nvis col-major (:392-394)

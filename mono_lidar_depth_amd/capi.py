@@ -133,6 +133,12 @@ class MldSemanticPlaneResult(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class MldRansacPlaneResult(C.Structure):
+    """mld_ransac_plane_result (include/mld.h): one sequence of mld_ransac_planes_estimate_device, 32 bytes."""
+    _fields_ = [("coeffs", C.c_float * 4), ("n_inliers", C.c_int32), ("iterations", C.c_int32), ("status", C.c_int32),
+                ("n_candidates", C.c_int32)]
+
+
 # Every symbol include/mld.h declares: (name, restype, argtypes)
 _P = C.POINTER
 _SIGNATURES = [
@@ -216,6 +222,11 @@ _SIGNATURES = [
     ("mld_semantic_planes_last_error", C.c_char_p, [C.c_void_p]),
     ("mld_semantic_planes_estimate_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64), C.c_int, _P(C.c_void_p)] +
      [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_double, C.c_void_p, _P(C.c_void_p)]),
+    ("mld_ransac_planes_create", C.c_void_p, [C.c_void_p, C.c_int, C.c_int64, _P(MldParams), _P(C.c_int)]),
+    ("mld_ransac_planes_destroy", None, [C.c_void_p]),
+    ("mld_ransac_planes_last_error", C.c_char_p, [C.c_void_p]),
+    ("mld_ransac_planes_estimate_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64), C.c_int, _P(C.c_uint32),
+                                                    C.c_void_p, _P(C.c_void_p)]),
     ("mld_get_visible_count", C.c_int, [C.c_void_p, C.c_int, _P(C.c_int64)]),
     ("mld_get_visible_image_points", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
     ("mld_get_point_index", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),

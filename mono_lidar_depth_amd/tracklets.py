@@ -164,7 +164,7 @@ class TrackletDepthModule:
 
 
 class _BatchObject:
-    """What TrackletStore, SemanticLabels and SemanticPlanes share: an object of the C-ABI (mld_<_NAME>_create /
+    """What TrackletStore, SemanticLabels, SemanticPlanes and RansacPlanes share: an object of the C-ABI (mld_<_NAME>_create /
     _destroy / _last_error) on an estimator's context, its handle in the attribute named _HANDLE, and the tensors of
     the calls that may still be queued."""
 
@@ -369,6 +369,56 @@ class SemanticPlanes(_BatchObject):
         self._hold((list(clouds), list(images), result_out, list(masks_out)))
 
 
+class RansacPlanes(_BatchObject):
+    """RansacPlane::CalculateInliersPlane (RansacPlane.cpp:41-140) for S sequences per call (mld_ransac_planes_*,
+    include/mld.h): per sequence the plane, the inlier count, PCL's iteration count, a status (1 = the reference's
+    ExceptionPclInvalid), the number of pass-through candidates and the inlier bitmask - bit for bit what
+    DepthEstimator.estimateGroundPlane gives for that cloud and seed, without a frame slot and before the projection.
+    `parameters` (default: the estimator's) is copied at creation.  Lists of S torch CUDA tensors in and out;
+    asynchronous on the estimator's stream.  Close it before its estimator."""
+
+    _NAME, _HANDLE = "ransac_planes", "_rp"
+
+    def __init__(self, estimator: DepthEstimator, n_seq: int, max_points: int, parameters=None):
+        self.S, self.max_points = int(n_seq), int(max_points)
+        P = parameters if parameters is not None else estimator.getParameters()
+        self._create(estimator, self.S, self.max_points, C.byref(P))
+
+    @staticmethod
+    def mask_words(n_points: int) -> int:
+        """32-bit words of the inlier mask of a cloud of n_points."""
+        return (int(n_points) + 31) // 32
+
+    def estimate(self, clouds, seeds, result_out, masks_out):
+        """clouds: S contiguous float32 CUDA tensors [n, 4] or [n, 8] of one width (an entry None: a sequence without
+        points); seeds: S integers; result_out: an int32 CUDA tensor [S, 8] that receives the records
+        (capi.MldRansacPlaneResult: coefficients as float bits, then n_inliers, iterations, status, n_candidates);
+        masks_out: S int32 CUDA tensors of at least mask_words(n) entries (None where the cloud is)."""
+        S = self.S
+        for name, ts in (("clouds", clouds), ("seeds", seeds), ("masks_out", masks_out)):
+            if len(ts) != S:
+                raise ValueError(f"{name}: expected {S} entries, one per sequence")
+        width = next((int(cl.shape[1]) for cl in clouds if cl is not None), 4)
+        ns = []
+        for s, cl in enumerate(clouds):
+            if cl is None:
+                ns.append(0)
+                continue
+            if cl.dim() != 2 or int(cl.shape[1]) != width or width not in (4, 8) or not cl.is_contiguous() or cl.element_size() != 4:
+                raise ValueError("clouds: contiguous float32 [n, 4] or [n, 8], one width for all sequences")
+            ns.append(int(cl.shape[0]))
+            if ns[s] and (masks_out[s] is None or
+                          int(masks_out[s].numel()) * masks_out[s].element_size() < 4 * self.mask_words(ns[s])):
+                raise ValueError(f"sequence {s}: masks_out holds fewer than {self.mask_words(ns[s])} words")
+        if tuple(result_out.shape) != (S, 8) or result_out.element_size() != 4 or not result_out.is_contiguous():
+            raise ValueError(f"result_out must be a contiguous int32 tensor [{S}, 8]")
+        vp = self._ptrs
+        self._check(self._lib.mld_ransac_planes_estimate_device(
+            self._rp, vp(clouds), (C.c_int64 * S)(*ns), 4 * width, (C.c_uint32 * S)(*[int(x) & 0xFFFFFFFF for x in seeds]),
+            int(result_out.data_ptr()), vp(masks_out)))
+        self._hold((list(clouds), result_out, list(masks_out)))
+
+
 class TrackletBatch:
     """The tracklet layer for S independent sequences at once (mld_set_clouds_planes_range_device +
     mld_tracklets_depths_device): the estimator's frame slots are two banks of S slots, sequence s keeps its current
@@ -391,6 +441,7 @@ class TrackletBatch:
         self.store: Optional[TrackletStore] = None
         self.semantic_labels: Optional[SemanticLabels] = None
         self.planes: Optional[SemanticPlanes] = None
+        self.rplanes: Optional[RansacPlanes] = None
 
     def attach_planes(self, max_points: int = 1 << 19) -> SemanticPlanes:
         """The semantic ground plane estimator of the S sequences that semantic_planes() runs ahead of a step, for clouds
@@ -422,6 +473,35 @@ class TrackletBatch:
         host[:] = res.cpu().numpy()
         coeffs = np.ascontiguousarray(host[:, :4]).view(np.float32)
         return coeffs, masks, host[:, 6].copy(), host[:, 4:6].copy()
+
+    def attach_ransac_planes(self, max_points: int = 1 << 19) -> RansacPlanes:
+        """The RANSAC ground plane estimator of the S sequences that ransac_planes() runs ahead of a step - for frames
+        without a label image -, for clouds of up to max_points points (default: 128 beams x 4096, 66 KB of scratch per
+        sequence).  It takes the estimator's parameters as they are now."""
+        if self.rplanes is None:
+            self.rplanes = RansacPlanes(self.est, self.S, max_points)
+        return self.rplanes
+
+    def ransac_planes(self, clouds, seeds):
+        """The ground planes setInputCloud estimates by default (RansacPlane::CalculateInliersPlane, parameters
+        ransac_plane_*) for this frame's clouds, ready for prepare_step() / prepare(): returns (coeffs float32 [S, 4],
+        masks: S int32 CUDA tensors, status int32 [S], counts int32 [S, 3] = (n_candidates, n_inliers, iterations)).
+        One call on the GPU, then ONE device-to-host copy of 32 * S bytes and one synchronisation per batch, as
+        semantic_planes().  A sequence with status 1 (the reference's ExceptionPclInvalid) has zero coefficients and an
+        empty mask; what to do with its frame is the caller's decision.  attach_ransac_planes() first."""
+        import torch
+        if self.rplanes is None:
+            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.ransac_planes without attach_ransac_planes")
+        dev = clouds[0].device
+        masks = [torch.empty(max(1, RansacPlanes.mask_words(c.shape[0])), dtype=torch.int32, device=dev) for c in clouds]
+        res = torch.empty((self.S, 8), dtype=torch.int32, device=dev)
+        self.est._after_torch(clouds[0])
+        self.rplanes.estimate(clouds, seeds, res, masks)
+        host = np.empty((self.S, 8), dtype=np.int32)
+        self.est._check(self.est._lib.mld_synchronize(self.est._ctx))
+        host[:] = res.cpu().numpy()
+        coeffs = np.ascontiguousarray(host[:, :4]).view(np.float32)
+        return coeffs, masks, host[:, 6].copy(), np.ascontiguousarray(host[:, [7, 4, 5]])
 
     def attach_labels(self) -> SemanticLabels:
         """The label assignment of the S sequences that labels() queues behind a step."""
@@ -532,4 +612,7 @@ class TrackletBatch:
         if self.planes is not None:
             self.planes.close()
             self.planes = None
+        if self.rplanes is not None:
+            self.rplanes.close()
+            self.rplanes = None
         self.est.close()
