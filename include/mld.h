@@ -755,6 +755,69 @@ int mld_ransac_planes_estimate_device(mld_ransac_planes* rp, const void* const* 
                                       uint32_t* const* mask_out_dev);
 
 /*
+ * Projected clouds of a batch — the frame's PointcloudData (PointcloudData.h:13-68; DepthEstimator.cpp:155-218) for n_seq
+ * independent sequences in one call: the visible list (getPointsCloudImageCs), _pointIndex, getPointDepthCamVisible, the
+ * camera-frame cloud (getCloudCameraCs) and the reference-format pixel map _img_points_lidar (NeighborFinderPixel.cpp:
+ * 38-55) - what the ROS layer's PublishImageProjectionCloud and PublishPointCloudCameraCs read.  What the debug / parity
+ * getters below do for one slot (device memory allocated per slot, a synchronisation and a copy to the host per getter)
+ * this does for all sequences with up to four launches, into DEVICE arrays of the caller, with no synchronisation: clouds
+ * are read where they lie, no slot is involved.
+ *
+ * mld_projected_clouds_create: an object bound to `ctx` (its stream, its device) for calls of n_seq (1 .. 65536) sequences
+ *   of up to max_points (1 .. 8 388 607) points each.  Of `camera` the width, height, focal length and principal point are
+ *   read, and T_cam_lidar (row-major 3x4): pass the values the context was created with.  All memory is allocated here,
+ *   none per call:
+ *     device  n_seq * (8 * ceil(max_points / 64) + 4 * ceil(max_points / 1024) + 60) bytes
+ *             (visibility mask per 64 points, visible count per 1024 points; descriptor)
+ *     pinned  16 * 56 * n_seq bytes   (the descriptor ring)
+ *   The sizes are checked before the context is looked at, then the context, then camera and T_cam_lidar (null; width or
+ *   height < 1; width * height beyond 2^31 - 1).  Returns NULL on failure with the reason in *status_out (optional) and
+ *   the text in mld_projected_clouds_last_error(NULL).  Destroy the object before its context.
+ *
+ * mld_projected_clouds_export_device: HOST tables of n_seq entries; every array they name is DEVICE memory, naturally
+ *   aligned for its element type.
+ *   pts_dev[s], n[s]    the cloud of sequence s: n[s] records of stride_bytes (16 or 32, x y z first), 4-byte aligned.
+ *                       0 <= n[s] <= max_points (beyond it: MLD_ERR_CAPACITY).
+ *   A point is VISIBLE iff its projection (u, v) - the exact f64 arithmetic of the depth path - satisfies 0 <= u <= W &&
+ *   0 <= v <= H and 0 < u < W && 0 < v < H (DepthEstimator.cpp:184-207).  NaN and inf are not visible, z_cam == 0 is not;
+ *   a point with z_cam < 0 may be.  Visible point r of a sequence is the r-th visible point in cloud order.
+ *   n_visible_out_dev   required: DEVICE array of n_seq int64, [s] = Nvis of sequence s.  Always complete.
+ *   uv_out[s]           2 x capacity[s] f64, column-major: (u, v) of visible point r at [2 r], [2 r + 1].
+ *   index_out[s]        capacity[s] int32: the original index of visible point r (_pointIndex).
+ *   depth_out           optional (the table, or single entries): capacity[s] f64, z_cam of visible point r
+ *                       (getPointDepthCamVisible(r)).
+ *   capacity[s]         >= 0.  Positions r >= capacity[s] are not written and nothing at or beyond min(Nvis, capacity[s])
+ *                       is touched; n_visible_out_dev[s] > capacity[s] tells a truncated sequence.  capacity[s] = n[s]
+ *                       never truncates; capacity[s] == 0 needs none of the three arrays.
+ *   cam_out             optional (the table, or single entries): 3 x n[s] f64 column-major, the camera-frame coordinates
+ *                       of ALL points (getCloudCameraCs) - not compacted, not subject to capacity.
+ *   map_out             optional (the table, or single entries): W * H int32 at index x + y * W, the VISIBLE index of the
+ *                       first visible point with z_cam > 0 whose ((int)u, (int)v) is that cell, else -1.  Every cell is
+ *                       written on every call.  The values come from the complete ranks: the map of a truncated sequence
+ *                       may hold values >= capacity[s].
+ *   n[s] == 0 needs no arrays and gets n_visible 0, and its map (if given) all -1.
+ *   Per sequence the outputs are bit for bit what mld_get_visible_count, mld_get_visible_image_points,
+ *   mld_get_point_index, mld_get_cloud_camera_cs, mld_get_pixel_map and mld_get_point_depth_cam_visible give on a slot
+ *   that holds that cloud (same transform and projection, operation for operation).
+ *   Asynchronous on the context's stream: no synchronisation, no host read of device data, no runtime call per sequence.
+ *   The host tables are consumed before the call returns, so a caller may queue frames ahead; the device arrays must stay
+ *   valid until the work has run.  Like a context, the object serves one call at a time.
+ *   MLD_ERR_INVALID_ARG with a text naming the argument (mld_projected_clouds_last_error; of NULL for a null object) on:
+ *   a null object, a null table pts_dev, n, capacity, uv_out or index_out, a null n_visible_out_dev, a null cloud of a
+ *   sequence with points, a null uv_out[s] or index_out[s] of a sequence with points and capacity, n[s] < 0,
+ *   capacity[s] < 0, a stride other than 16 or 32, a cloud that is not 4-byte aligned.
+ */
+typedef struct mld_projected_clouds mld_projected_clouds;
+mld_projected_clouds* mld_projected_clouds_create(mld_ctx* ctx, int n_seq, int64_t max_points, const mld_camera* camera,
+                                                  const double T_cam_lidar[12], int* status_out);
+void mld_projected_clouds_destroy(mld_projected_clouds* pc);
+const char* mld_projected_clouds_last_error(const mld_projected_clouds* pc);
+int mld_projected_clouds_export_device(mld_projected_clouds* pc, const void* const* pts_dev, const int64_t* n,
+                                       int stride_bytes, const int64_t* capacity, int64_t* n_visible_out_dev,
+                                       double* const* uv_out, int32_t* const* index_out, double* const* depth_out,
+                                       double* const* cam_out, int32_t* const* map_out);
+
+/*
  * Debug / parity getters (host buffers; each synchronises).
  *   mld_get_visible_count           -> _points_cs_image_visible.cols()         (DepthEstimator.cpp:192)
  *   mld_get_visible_image_points    -> getPointsCloudImageCs, 2 x Nvis col-major (:392-394)

@@ -227,6 +227,11 @@ _SIGNATURES = [
     ("mld_ransac_planes_last_error", C.c_char_p, [C.c_void_p]),
     ("mld_ransac_planes_estimate_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64), C.c_int, _P(C.c_uint32),
                                                     C.c_void_p, _P(C.c_void_p)]),
+    ("mld_projected_clouds_create", C.c_void_p, [C.c_void_p, C.c_int, C.c_int64, _P(MldCamera), _P(C.c_double), _P(C.c_int)]),
+    ("mld_projected_clouds_destroy", None, [C.c_void_p]),
+    ("mld_projected_clouds_last_error", C.c_char_p, [C.c_void_p]),
+    ("mld_projected_clouds_export_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64), C.c_int, _P(C.c_int64),
+                                                     C.c_void_p] + [_P(C.c_void_p)] * 5),
     ("mld_get_visible_count", C.c_int, [C.c_void_p, C.c_int, _P(C.c_int64)]),
     ("mld_get_visible_image_points", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
     ("mld_get_point_index", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),

@@ -14,7 +14,8 @@ stored tracks in message order, and TrackletBatch.step runs a whole frame of eve
 (mld_labels_*) is the node that follows tracklets_depth in the reference's launch files: the label of every track by
 majority vote in a window of a label image (matches_conversion_ros_tool, semantic_labels.cpp:50-72).  SemanticPlanes
 (mld_semantic_planes_*) is the ground plane process() builds from the label image of every frame (:269-284), for all
-sequences of a batch in one call and ahead of the projection.
+sequences of a batch in one call and ahead of the projection.  ProjectedClouds (mld_projected_clouds_*) is the frame's
+PointcloudData - visible list, point index, camera-frame cloud, pixel map - of all sequences as device tensors.
 """
 from __future__ import annotations
 
@@ -164,7 +165,7 @@ class TrackletDepthModule:
 
 
 class _BatchObject:
-    """What TrackletStore, SemanticLabels, SemanticPlanes and RansacPlanes share: an object of the C-ABI (mld_<_NAME>_create /
+    """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes and ProjectedClouds share: an object of the C-ABI (mld_<_NAME>_create /
     _destroy / _last_error) on an estimator's context, its handle in the attribute named _HANDLE, and the tensors of
     the calls that may still be queued."""
 
@@ -419,6 +420,77 @@ class RansacPlanes(_BatchObject):
         self._hold((list(clouds), result_out, list(masks_out)))
 
 
+class ProjectedClouds(_BatchObject):
+    """The frame's PointcloudData (DepthEstimator.cpp:155-218, NeighborFinderPixel.cpp:38-55) for S sequences per call
+    (mld_projected_clouds_*, include/mld.h): per sequence the visible list (getPointsCloudImageCs), _pointIndex,
+    getPointDepthCamVisible, the camera-frame cloud (getCloudCameraCs) and the reference-format pixel map - bit for bit
+    what the one-slot getters (getPointsCloudImageCs ... getPixelMap) give for that cloud, without a frame slot and into
+    device tensors.  Lists of S torch CUDA tensors in and out; asynchronous on the estimator's stream.  Close it before its
+    estimator."""
+
+    _NAME, _HANDLE = "projected_clouds", "_pc"
+
+    def __init__(self, estimator: DepthEstimator, n_seq: int, max_points: int):
+        self.S, self.max_points = int(n_seq), int(max_points)
+        cam = estimator._camera.as_struct()
+        self.width, self.height = int(cam.width), int(cam.height)
+        T = np.ascontiguousarray(np.asarray(estimator._T, dtype=np.float64).reshape(-1)[:12])
+        self._create(estimator, self.S, self.max_points, C.byref(cam), T.ctypes.data_as(C.POINTER(C.c_double)))
+
+    def export(self, clouds, capacity, n_visible, uv, index, depth=None, cam=None, pixel_map=None):
+        """clouds: S contiguous float32 CUDA tensors [n, 4] or [n, 8] of one width (an entry None: a sequence without
+        points); capacity: S integers, or None (= n, never truncated); n_visible: an int64 CUDA tensor [S]; uv: S float64
+        CUDA tensors of at least 2 * min(capacity, n) entries ((u, v) of visible point r at [2 r], [2 r + 1]: a
+        contiguous [capacity, 2]); index: S int32 CUDA tensors of at least min(capacity, n) entries; depth: None, or S
+        float64 CUDA tensors of that length; cam: None, or S float64 CUDA tensors of 3 * n entries (a contiguous [n, 3]);
+        pixel_map: None, or S int32 CUDA tensors of height * width entries.  Single entries of uv and index may be None
+        where min(capacity, n) is 0, of depth, cam and pixel_map anywhere.  Visible points at or beyond a sequence's
+        capacity are dropped, which the caller sees from n_visible[s] > capacity[s]; the map is not affected."""
+        S = self.S
+        for name, ts in (("clouds", clouds), ("capacity", capacity), ("uv", uv), ("index", index), ("depth", depth),
+                         ("cam", cam), ("pixel_map", pixel_map)):
+            if ts is not None and len(ts) != S:
+                raise ValueError(f"{name}: expected {S} entries, one per sequence")
+        if tuple(n_visible.shape) != (S,) or n_visible.element_size() != 8 or not n_visible.is_contiguous():
+            raise ValueError(f"n_visible must be a contiguous int64 tensor [{S}]")
+        width = next((int(cl.shape[1]) for cl in clouds if cl is not None), 4)
+        ns, caps = [], []
+
+        def holds(ts, s, entries, size, name, required):
+            t = ts[s] if ts is not None else None
+            if t is None:
+                if required and entries:
+                    raise ValueError(f"sequence {s}: {name} is missing")
+                return
+            if t.element_size() != size or not t.is_contiguous() or int(t.numel()) < entries:
+                raise ValueError(f"sequence {s}: {name} must be contiguous, of {size}-byte elements, at least {entries} of them")
+
+        for s, cl in enumerate(clouds):
+            n = 0
+            if cl is not None:
+                if cl.dim() != 2 or int(cl.shape[1]) != width or width not in (4, 8) or not cl.is_contiguous() or cl.element_size() != 4:
+                    raise ValueError("clouds: contiguous float32 [n, 4] or [n, 8], one width for all sequences")
+                n = int(cl.shape[0])
+            cap = n if capacity is None else int(capacity[s])
+            if cap < 0:
+                raise ValueError(f"sequence {s}: negative capacity")
+            ns.append(n)
+            caps.append(cap)
+            m = min(cap, n)
+            holds(uv, s, 2 * m, 8, "uv", True)
+            holds(index, s, m, 4, "index", True)
+            holds(depth, s, m, 8, "depth", False)
+            holds(cam, s, 3 * n, 8, "cam", False)
+            holds(pixel_map, s, self.width * self.height, 4, "pixel_map", False)
+        vp = self._ptrs
+        self._check(self._lib.mld_projected_clouds_export_device(
+            self._pc, vp(clouds), (C.c_int64 * S)(*ns), 4 * width, (C.c_int64 * S)(*caps), int(n_visible.data_ptr()), vp(uv),
+            vp(index), vp(depth) if depth is not None else None, vp(cam) if cam is not None else None,
+            vp(pixel_map) if pixel_map is not None else None))
+        self._hold((list(clouds), n_visible, list(uv), list(index), list(depth) if depth is not None else None,
+                    list(cam) if cam is not None else None, list(pixel_map) if pixel_map is not None else None))
+
+
 class TrackletBatch:
     """The tracklet layer for S independent sequences at once (mld_set_clouds_planes_range_device +
     mld_tracklets_depths_device): the estimator's frame slots are two banks of S slots, sequence s keeps its current
@@ -442,6 +514,7 @@ class TrackletBatch:
         self.semantic_labels: Optional[SemanticLabels] = None
         self.planes: Optional[SemanticPlanes] = None
         self.rplanes: Optional[RansacPlanes] = None
+        self.pclouds: Optional[ProjectedClouds] = None
 
     def attach_planes(self, max_points: int = 1 << 19) -> SemanticPlanes:
         """The semantic ground plane estimator of the S sequences that semantic_planes() runs ahead of a step, for clouds
@@ -502,6 +575,40 @@ class TrackletBatch:
         host[:] = res.cpu().numpy()
         coeffs = np.ascontiguousarray(host[:, :4]).view(np.float32)
         return coeffs, masks, host[:, 6].copy(), np.ascontiguousarray(host[:, [7, 4, 5]])
+
+    def attach_projected_clouds(self, max_points: int = 1 << 19) -> ProjectedClouds:
+        """The export of the projected clouds of the S sequences that projected_clouds() runs, for clouds of up to
+        max_points points (default: 128 beams x 4096, 66 KB of scratch per sequence)."""
+        if self.pclouds is None:
+            self.pclouds = ProjectedClouds(self.est, self.S, max_points)
+        return self.pclouds
+
+    def projected_clouds(self, clouds, depth: bool = False, cam: bool = False, pixel_map: bool = False, capacity=None):
+        """The PointcloudData of this frame's clouds as device tensors - what the ROS layer's PublishImageProjectionCloud
+        (uv) and PublishPointCloudCameraCs (cam) read: returns a dict with n_visible (int64 [S]), uv (S float64 [capacity,
+        2]), index (S int32 [capacity]) and, where asked for, depth (S float64 [capacity]), cam (S float64 [n, 3]) and
+        pixel_map (S int32 [height, width]); the rows at and beyond n_visible[s] are not written.  capacity: S integers,
+        or None (= n, never truncated).  One call on the GPU and no synchronisation: torch's current stream is made to
+        wait for the export, so torch operations may consume the tensors at once; a host read synchronises as usual.
+        attach_projected_clouds() first."""
+        import torch
+        if self.pclouds is None:
+            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED,
+                                      "TrackletBatch.projected_clouds without attach_projected_clouds")
+        pc = self.pclouds
+        dev = next((c.device for c in clouds if c is not None), torch.device("cuda", self.est._device))
+        ns = [int(c.shape[0]) if c is not None else 0 for c in clouds]
+        caps = [min(int(capacity[s]), ns[s]) if capacity is not None else ns[s] for s in range(self.S)]
+        out = {"n_visible": torch.empty(self.S, dtype=torch.int64, device=dev),
+               "uv": [torch.empty((m, 2), dtype=torch.float64, device=dev) for m in caps],
+               "index": [torch.empty(m, dtype=torch.int32, device=dev) for m in caps],
+               "depth": [torch.empty(m, dtype=torch.float64, device=dev) for m in caps] if depth else None,
+               "cam": [torch.empty((n, 3), dtype=torch.float64, device=dev) for n in ns] if cam else None,
+               "pixel_map": [torch.empty((pc.height, pc.width), dtype=torch.int32, device=dev) for _ in ns] if pixel_map else None}
+        self.est._after_torch(*[c for c in clouds if c is not None][:1])
+        pc.export(clouds, caps, out["n_visible"], out["uv"], out["index"], out["depth"], out["cam"], out["pixel_map"])
+        self.est.orderTorchAfter()
+        return out
 
     def attach_labels(self) -> SemanticLabels:
         """The label assignment of the S sequences that labels() queues behind a step."""
@@ -615,4 +722,7 @@ class TrackletBatch:
         if self.rplanes is not None:
             self.rplanes.close()
             self.rplanes = None
+        if self.pclouds is not None:
+            self.pclouds.close()
+            self.pclouds = None
         self.est.close()
