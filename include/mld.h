@@ -818,6 +818,99 @@ int mld_projected_clouds_export_device(mld_projected_clouds* pc, const void* con
                                        double* const* cam_out, int32_t* const* map_out);
 
 /*
+ * Depth reports of a batch — the two per-frame products of the reference's ROS node (tracklets_depth_ros_tool,
+ * tracklet_depth_interface.cpp:171-297) besides tracklets, camera-frame cloud and image projection, for n_seq independent
+ * sequences in one call:
+ *   the depth-calculation statistics  getDepthCalcStats (DepthEstimator.cpp:400-402), filled by LogDepthCalcStats
+ *                                     (:1039-1090), published by PublishDepthCalcStats: one mld_depth_report per sequence
+ *   the interpolated cloud            getCloudInterpolated (:339-341), published by PublishPointCloudInterpolated: the
+ *                                     intersection point of the viewing ray with the local plane, one per feature with a
+ *                                     depth
+ * What mld_result_histogram does for one resultType array in host memory, and the host shim's getCloudInterpolated from the
+ * debug vectors of a host-input call, this does for all sequences with at most three launches, from DEVICE arrays into
+ * DEVICE arrays of the caller, with no synchronisation.
+ *
+ * mld_depth_report (192 bytes, 8-byte aligned):
+ *   counts[t]       features of DepthResultType t, as mld_result_histogram
+ *   other           features whose type lies outside [0, MLD_RESULT_TYPE_COUNT): dropped by mld_result_histogram, counted
+ *                   here
+ *   point_count     n_features[s] - DepthCalculationStatistics::SetPointCount(featuresCount) (DepthEstimator.cpp:484)
+ *   n_interpolated  features with depth >= 0
+ *
+ * mld_depth_reports_create: an object bound to `ctx` (its stream, its device) for calls of n_seq (1 .. 65536) sequences
+ *   of up to max_features (1 .. 16 777 216) features each.  Of `camera` the focal length and the principal point are
+ *   read: pass the values the context was created with.  All memory is allocated here, none per call:
+ *     device  n_seq * (8 * ceil(max_features / 64) + 92 * ceil(max_features / 1024) + 60) bytes
+ *             (validity mask per 64 features; valid count and 22-bin type histogram per 1024 features; descriptor)
+ *     pinned  16 * 56 * n_seq bytes   (the descriptor ring)
+ *   The sizes are checked before the context is looked at, then the context, then the camera (null; focal_length not
+ *   finite or 0).  Returns NULL on failure with the reason in *status_out (optional) and the text in
+ *   mld_depth_reports_last_error(NULL).  Destroy the object before its context.
+ *
+ * mld_depth_reports_collect_device (DepthEstimator layer) and mld_depth_reports_collect_tracks_device (tracklet layer):
+ *   HOST tables of n_seq entries; every array they name is DEVICE memory, naturally aligned for its element type.
+ *   n_features[s]       0 <= n_features[s] <= max_features (beyond it: MLD_ERR_CAPACITY).
+ *   collect_device      the arrays of mld_calculate_depths_device: uv[s] 2 x n_features[s] f64 column-major ((u, v) of
+ *                       feature i at [2 i], [2 i + 1]), depth[s] f64, type[s] int32.
+ *   collect_tracks_device  the arrays of mld_tracklets_depths_device / mld_tracklets_step_device: u[s], v[s] (u_new,
+ *                       v_new) and depth[s] (d_cur) f32, type[s] (type_cur) int32.  d = (double)depth and
+ *                       u = (double)truncf(u), likewise v: the integer pixel the tracklet layer evaluates
+ *                       (std::pair<int,int>).  It equals (double)(int)u wherever that conversion is defined, and is
+ *                       defined for NaN, +-inf and values beyond int as well.  This form serves the CURRENT-frame
+ *                       results (d_cur, type_cur): they are what the reference's statistics hold after process(),
+ *                       because the current-frame CalculateDepth runs last and clears them.  d_last is written only for
+ *                       new tracks and is not a valid input.
+ *   type                the table, or single entries, may be NULL: counts and other of those sequences are 0;
+ *                       point_count and n_interpolated are still filled.
+ *   report_out_dev      required: ONE device array of n_seq records.  Every record is written completely on every call;
+ *                       a sequence with 0 features gets an all-zero record (and needs no arrays).
+ *   A feature is INTERPOLATED iff depth >= 0, whatever its type says: NaN is out, -0.0 and +inf are in (as in the host
+ *   shim's getCloudInterpolated, host/monolidar_fusion/DepthEstimator.h).  Its point is, in f64 and operation for
+ *   operation as there and in depth_estimator.py,
+ *       x = (u - cu) / f * d,   y = (v - cv) / f * d,   z = d.
+ *   The reference's own push into this cloud is commented out (DepthEstimator.cpp:1028-1034), so its cloud is always
+ *   empty; as with the existing getters, this is what the member is documented to hold (DepthEstimator.h:328).
+ *   points_out[s]       capacity[s] x 3 f64: the points of the interpolated features IN FEATURE ORDER, point r at [3 r],
+ *                       [3 r + 1], [3 r + 2].
+ *   feature_out[s]      optional (the table, or single entries): capacity[s] int32, the feature index point r came from -
+ *                       with it a caller joins the points with track ids.
+ *   The points_out table may be NULL: statistics only; capacity and feature_out are then ignored.  With points_out,
+ *   capacity is required and capacity[s] >= 0.  Points of rank >= capacity[s] are not written and nothing at or beyond
+ *   min(n_interpolated, capacity[s]) is touched; n_interpolated is always complete, so n_interpolated > capacity[s] tells
+ *   a truncated sequence.  capacity[s] = n_features[s] never truncates; capacity[s] == 0 needs neither array.
+ *   Asynchronous on the context's stream: no synchronisation, no host read of device data, no runtime call per sequence,
+ *   nothing allocated per call.  The host tables are consumed before the call returns, so a caller may queue frames
+ *   ahead; the device arrays must stay valid until the work has run.  Like a context, the object serves one call at a
+ *   time.
+ *   MLD_ERR_INVALID_ARG with a text naming the function and the argument (mld_depth_reports_last_error; "null object
+ *   (dr)" of NULL for a null object) on: a null object, a null table uv / u / v / depth / n_features, a null
+ *   report_out_dev, a null input array of a sequence with features, n_features[s] < 0, a null capacity table with
+ *   points_out, capacity[s] < 0, a null points_out[s] where min(capacity[s], n_features[s]) > 0, a float64 array or
+ *   report_out_dev that is not 8-byte aligned, a float32 or int32 array that is not 4-byte aligned.
+ */
+typedef struct mld_depth_report {
+    int64_t counts[MLD_RESULT_TYPE_COUNT];
+    int64_t other;
+    int64_t point_count;
+    int64_t n_interpolated;
+} mld_depth_report;
+
+typedef struct mld_depth_reports mld_depth_reports;
+mld_depth_reports* mld_depth_reports_create(mld_ctx* ctx, int n_seq, int64_t max_features, const mld_camera* camera,
+                                            int* status_out);
+void mld_depth_reports_destroy(mld_depth_reports* dr);
+const char* mld_depth_reports_last_error(const mld_depth_reports* dr);
+int mld_depth_reports_collect_device(mld_depth_reports* dr, const double* const* uv, const double* const* depth,
+                                     const int32_t* const* type, const int64_t* n_features, const int64_t* capacity,
+                                     mld_depth_report* report_out_dev, double* const* points_out,
+                                     int32_t* const* feature_out);
+int mld_depth_reports_collect_tracks_device(mld_depth_reports* dr, const float* const* u, const float* const* v,
+                                            const float* const* depth, const int32_t* const* type,
+                                            const int64_t* n_features, const int64_t* capacity,
+                                            mld_depth_report* report_out_dev, double* const* points_out,
+                                            int32_t* const* feature_out);
+
+/*
  * Debug / parity getters (host buffers; each synchronises).
  *   mld_get_visible_count           -> _points_cs_image_visible.cols()         (DepthEstimator.cpp:192)
  *   mld_get_visible_image_points    -> getPointsCloudImageCs, 2 x Nvis col-major (:392-394)

@@ -139,6 +139,11 @@ class MldRansacPlaneResult(C.Structure):
                 ("n_candidates", C.c_int32)]
 
 
+class MldDepthReport(C.Structure):
+    """mld_depth_report (include/mld.h): one sequence of mld_depth_reports_collect_*_device, 192 bytes = 24 int64."""
+    _fields_ = [("counts", C.c_int64 * MLD_RESULT_TYPE_COUNT), ("other", C.c_int64), ("point_count", C.c_int64), ("n_interpolated", C.c_int64)]
+
+
 # Every symbol include/mld.h declares: (name, restype, argtypes)
 _P = C.POINTER
 _SIGNATURES = [
@@ -232,6 +237,13 @@ _SIGNATURES = [
     ("mld_projected_clouds_last_error", C.c_char_p, [C.c_void_p]),
     ("mld_projected_clouds_export_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64), C.c_int, _P(C.c_int64),
                                                      C.c_void_p] + [_P(C.c_void_p)] * 5),
+    ("mld_depth_reports_create", C.c_void_p, [C.c_void_p, C.c_int, C.c_int64, _P(MldCamera), _P(C.c_int)]),
+    ("mld_depth_reports_destroy", None, [C.c_void_p]),
+    ("mld_depth_reports_last_error", C.c_char_p, [C.c_void_p]),
+    ("mld_depth_reports_collect_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 3 + [_P(C.c_int64)] * 2 +
+     [C.c_void_p] + [_P(C.c_void_p)] * 2),
+    ("mld_depth_reports_collect_tracks_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 4 + [_P(C.c_int64)] * 2 +
+     [C.c_void_p] + [_P(C.c_void_p)] * 2),
     ("mld_get_visible_count", C.c_int, [C.c_void_p, C.c_int, _P(C.c_int64)]),
     ("mld_get_visible_image_points", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
     ("mld_get_point_index", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),

@@ -16,6 +16,8 @@ majority vote in a window of a label image (matches_conversion_ros_tool, semanti
 (mld_semantic_planes_*) is the ground plane process() builds from the label image of every frame (:269-284), for all
 sequences of a batch in one call and ahead of the projection.  ProjectedClouds (mld_projected_clouds_*) is the frame's
 PointcloudData - visible list, point index, camera-frame cloud, pixel map - of all sequences as device tensors.
+DepthReports (mld_depth_reports_*) is the depth-calculation statistics (getDepthCalcStats) and the interpolated cloud
+(getCloudInterpolated) of all sequences, from device tensors into device tensors.
 """
 from __future__ import annotations
 
@@ -165,7 +167,7 @@ class TrackletDepthModule:
 
 
 class _BatchObject:
-    """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes and ProjectedClouds share: an object of the C-ABI (mld_<_NAME>_create /
+    """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes, ProjectedClouds and DepthReports share: an object of the C-ABI (mld_<_NAME>_create /
     _destroy / _last_error) on an estimator's context, its handle in the attribute named _HANDLE, and the tensors of
     the calls that may still be queued."""
 
@@ -491,6 +493,115 @@ class ProjectedClouds(_BatchObject):
                     list(cam) if cam is not None else None, list(pixel_map) if pixel_map is not None else None))
 
 
+class DepthReports(_BatchObject):
+    """The depth-calculation statistics (getDepthCalcStats, DepthEstimator.cpp:1039-1090) and the interpolated cloud
+    (getCloudInterpolated: the point (u - cu) / f * d, (v - cv) / f * d, d of every feature with depth >= 0, in feature
+    order) for S sequences per call (mld_depth_reports_*, include/mld.h), from device tensors into device tensors.
+    collect() takes the arrays of the DepthEstimator layer (float64 uv, float64 depths), collect_tracks() those of the
+    tracklet layer (float32 u, v, depths of the CURRENT frame; u and v are truncated to the integer pixel).  Lists of S
+    torch CUDA tensors in and out; asynchronous on the estimator's stream.  Close it before its estimator."""
+
+    _NAME, _HANDLE = "depth_reports", "_dr"
+    WORDS = 24  # int64 words of a record (capi.MldDepthReport): counts[21], other, point_count, n_interpolated
+
+    def __init__(self, estimator: DepthEstimator, n_seq: int, max_features: int):
+        self.S, self.max_features = int(n_seq), int(max_features)
+        cam = estimator._camera.as_struct()
+        self._create(estimator, self.S, self.max_features, C.byref(cam))
+
+    def _outputs(self, ns, types, report, capacity, points, feature):
+        """Checks what both calls share; returns the capacity table (None without points)."""
+        S = self.S
+        for name, ts in (("types", types), ("capacity", capacity), ("points", points), ("feature", feature)):
+            if ts is not None and len(ts) != S:
+                raise ValueError(f"{name}: expected {S} entries, one per sequence")
+        if tuple(report.shape) != (S, self.WORDS) or report.element_size() != 8 or not report.is_contiguous():
+            raise ValueError(f"report must be a contiguous int64 tensor [{S}, {self.WORDS}]")
+        caps = None
+        for s, n in enumerate(ns):
+            t = types[s] if types is not None else None
+            if t is not None and (t.element_size() != 4 or not t.is_contiguous() or int(t.numel()) != n):
+                raise ValueError(f"sequence {s}: types must be a contiguous int32 tensor of {n} entries")
+        if points is not None:
+            caps = []
+            for s, n in enumerate(ns):
+                cap = n if capacity is None else int(capacity[s])
+                if cap < 0:
+                    raise ValueError(f"sequence {s}: negative capacity")
+                caps.append(cap)
+                m = min(cap, n)
+                for name, t, size, entries in (("points", points[s], 8, 3 * m),
+                                               ("feature", feature[s] if feature is not None else None, 4, m)):
+                    if t is None:
+                        if name == "points" and entries:
+                            raise ValueError(f"sequence {s}: points is missing")
+                        continue
+                    if t.element_size() != size or not t.is_contiguous() or int(t.numel()) < entries:
+                        raise ValueError(f"sequence {s}: {name} must be contiguous, of {size}-byte elements, at least {entries} of them")
+        return caps
+
+    def _inputs(self, s, n, size, **arrays):
+        for name, t in arrays.items():
+            if t is None:
+                if n:
+                    raise ValueError(f"sequence {s}: {name} is missing")
+                continue
+            if t.element_size() != size or not t.is_contiguous():
+                raise ValueError(f"sequence {s}: {name} must be contiguous, of {size}-byte elements")
+
+    def collect(self, uv, depth, types, report, capacity=None, points=None, feature=None):
+        """uv: S contiguous float64 CUDA tensors [n, 2] (an entry None: a sequence without features); depth: S float64
+        CUDA tensors [n]; types: None, or S int32 CUDA tensors [n] (single entries may be None): without them counts
+        and other are 0; report: an int64 CUDA tensor [S, 24] that receives the records (capi.MldDepthReport); points:
+        None (statistics only), or S float64 CUDA tensors of at least 3 * min(capacity, n) entries (a contiguous
+        [capacity, 3]); capacity: S integers, or None (= n, never truncated); feature: None, or S int32 CUDA tensors of
+        at least min(capacity, n) entries (single entries may be None).  Points at or beyond a sequence's capacity are
+        dropped, which the caller sees from n_interpolated > capacity."""
+        S = self.S
+        for name, ts in (("uv", uv), ("depth", depth)):
+            if len(ts) != S:
+                raise ValueError(f"{name}: expected {S} entries, one per sequence")
+        ns = []
+        for s in range(S):
+            n = int(depth[s].numel()) if depth[s] is not None else 0
+            self._inputs(s, n, 8, uv=uv[s], depth=depth[s])
+            if uv[s] is not None and int(uv[s].numel()) != 2 * n:
+                raise ValueError(f"sequence {s}: uv must hold 2 x {n} entries")
+            ns.append(n)
+        caps = self._outputs(ns, types, report, capacity, points, feature)
+        vp = self._ptrs
+        self._check(self._lib.mld_depth_reports_collect_device(
+            self._dr, vp(uv), vp(depth), vp(types) if types is not None else None, (C.c_int64 * S)(*ns),
+            (C.c_int64 * S)(*caps) if caps is not None else None, int(report.data_ptr()),
+            vp(points) if points is not None else None, vp(feature) if feature is not None and points is not None else None))
+        self._hold((list(uv), list(depth), list(types) if types is not None else None, report,
+                    list(points) if points is not None else None, list(feature) if feature is not None else None))
+
+    def collect_tracks(self, u, v, depth, types, report, capacity=None, points=None, feature=None):
+        """As collect(), on the tensors of TrackletBatch.prepare_step() / prepare(): u, v (u_new, v_new), depth (d_cur):
+        S float32 CUDA tensors [n]; types (t_cur): None, or S int32 CUDA tensors [n]."""
+        S = self.S
+        for name, ts in (("u", u), ("v", v), ("depth", depth)):
+            if len(ts) != S:
+                raise ValueError(f"{name}: expected {S} entries, one per sequence")
+        ns = []
+        for s in range(S):
+            n = int(depth[s].numel()) if depth[s] is not None else 0
+            self._inputs(s, n, 4, u=u[s], v=v[s], depth=depth[s])
+            for name, t in (("u", u[s]), ("v", v[s])):
+                if t is not None and int(t.numel()) != n:
+                    raise ValueError(f"sequence {s}: {name} and depth differ in length")
+            ns.append(n)
+        caps = self._outputs(ns, types, report, capacity, points, feature)
+        vp = self._ptrs
+        self._check(self._lib.mld_depth_reports_collect_tracks_device(
+            self._dr, vp(u), vp(v), vp(depth), vp(types) if types is not None else None, (C.c_int64 * S)(*ns),
+            (C.c_int64 * S)(*caps) if caps is not None else None, int(report.data_ptr()),
+            vp(points) if points is not None else None, vp(feature) if feature is not None and points is not None else None))
+        self._hold((list(u), list(v), list(depth), list(types) if types is not None else None, report,
+                    list(points) if points is not None else None, list(feature) if feature is not None else None))
+
+
 class TrackletBatch:
     """The tracklet layer for S independent sequences at once (mld_set_clouds_planes_range_device +
     mld_tracklets_depths_device): the estimator's frame slots are two banks of S slots, sequence s keeps its current
@@ -515,6 +626,7 @@ class TrackletBatch:
         self.planes: Optional[SemanticPlanes] = None
         self.rplanes: Optional[RansacPlanes] = None
         self.pclouds: Optional[ProjectedClouds] = None
+        self.depth_reports: Optional[DepthReports] = None
 
     def attach_planes(self, max_points: int = 1 << 19) -> SemanticPlanes:
         """The semantic ground plane estimator of the S sequences that semantic_planes() runs ahead of a step, for clouds
@@ -610,6 +722,40 @@ class TrackletBatch:
         self.est.orderTorchAfter()
         return out
 
+    def attach_reports(self) -> DepthReports:
+        """The statistics and interpolated clouds of the S sequences that reports() queues behind a step, for up to
+        max_tracks tracks per sequence."""
+        if self.depth_reports is None:
+            self.depth_reports = DepthReports(self.est, self.S, self.max_tracks)
+        return self.depth_reports
+
+    def reports(self, f, points: bool = False, capacity=None):
+        """The depth-calculation statistics of the tracks of table `f` (prepare_step() / prepare()) and, with points, their
+        interpolated clouds - what the ROS layer's PublishDepthCalcStats and PublishPointCloudInterpolated read -, queued
+        on the estimator's stream behind the step() / run() of `f` when called after it: DepthReports.collect_tracks on
+        the table's u_new, v_new, d_cur and t_cur (t_cur None: counts and other are 0).  Returns a dict with report
+        (int64 [S, 24]: counts[21], other, point_count, n_interpolated), points (S float64 [capacity, 3], or None) and
+        feature (S int32 [capacity]: the track each point belongs to, or None); rows at and beyond n_interpolated are
+        not written.  capacity: S integers, or None (= the number of tracks, never truncated).  No synchronisation:
+        torch's current stream is made to wait for the call, so torch operations may consume the tensors at once; a
+        host read synchronises as usual.  attach_reports() first."""
+        import torch
+        if self.depth_reports is None:
+            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.reports without attach_reports")
+        u_new, v_new = f["features"]
+        d_cur, t_cur = f["current"]
+        dev = next((t.device for t in d_cur if t is not None), torch.device("cuda", self.est._device))
+        ns = [int(t.numel()) for t in d_cur]
+        caps = [min(int(capacity[s]), ns[s]) if capacity is not None else ns[s] for s in range(self.S)]
+        out = {"report": torch.empty((self.S, DepthReports.WORDS), dtype=torch.int64, device=dev),
+               "points": [torch.empty((m, 3), dtype=torch.float64, device=dev) for m in caps] if points else None,
+               "feature": [torch.empty(m, dtype=torch.int32, device=dev) for m in caps] if points else None}
+        self.est._after_torch(*d_cur[:1])
+        self.depth_reports.collect_tracks(u_new, v_new, d_cur, t_cur, out["report"], caps if points else None,
+                                          out["points"], out["feature"])
+        self.est.orderTorchAfter()
+        return out
+
     def attach_labels(self) -> SemanticLabels:
         """The label assignment of the S sequences that labels() queues behind a step."""
         if self.semantic_labels is None:
@@ -644,7 +790,8 @@ class TrackletBatch:
                 "t_last": vp(t_last) if t_last is not None else None,
                 "keep": (list(clouds), list(masks), list(ids), list(u_new), list(v_new), list(u_old), list(v_old),
                          list(d_cur), list(d_last), t_cur, t_last),
-                "features": (list(u_new), list(v_new))}
+                "features": (list(u_new), list(v_new)),
+                "current": (list(d_cur), list(t_cur) if t_cur is not None else None)}
 
     def step(self, f, nxt: Optional["TrackletBatch"] = None, handover: str = "projection"):
         """run() with the tracklet maps on the GPU (mld_tracklets_step_device): projection of the current bank, then
@@ -682,7 +829,8 @@ class TrackletBatch:
                 "t_last": vp(t_last) if t_last is not None else None,
                 "keep": (list(clouds), list(masks), list(u_new), list(v_new), list(u_old), list(v_old), list(is_new),
                          list(d_cur), list(d_last), t_cur, t_last),
-                "features": (list(u_new), list(v_new))}
+                "features": (list(u_new), list(v_new)),
+                "current": (list(d_cur), list(t_cur) if t_cur is not None else None)}
 
     def run(self, f, nxt: Optional["TrackletBatch"] = None, handover: str = "projection"):
         """One frame of every sequence from prepared tables: projection of the current bank, then the tracklet call.
@@ -725,4 +873,7 @@ class TrackletBatch:
         if self.pclouds is not None:
             self.pclouds.close()
             self.pclouds = None
+        if self.depth_reports is not None:
+            self.depth_reports.close()
+            self.depth_reports = None
         self.est.close()
