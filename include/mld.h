@@ -911,6 +911,81 @@ int mld_depth_reports_collect_tracks_device(mld_depth_reports* dr, const float* 
                                             int32_t* const* feature_out);
 
 /*
+ * Ground-plane inliers of a batch — what the reference keeps on a frame's GroundPlane besides the coefficients, for n_seq
+ * independent sequences in one call:
+ *   the inlier indices       GroundPlane::getInlinersIndex (RansacPlane.h:109): ascending original indices
+ *   the lidar-frame matrix   GroundPlane::getMatrixFromIndices (RansacPlane.cpp:142-151): the float x, y, z of the inliers
+ *   the camera-frame cloud   DepthEstimator::getCloudRansacPlane (DepthEstimator.cpp:294-308,396-398): the inliers in the
+ *                            camera frame, filtered by ransac_plane_use_camx_treshold / ransac_plane_treshold_camx
+ * The input is the inlier bitmask mld_semantic_planes_estimate_device and mld_ransac_planes_estimate_device write and
+ * mld_set_clouds_planes_range_device takes.  What mld_get_ground_plane_inliers and mld_get_ground_plane_cloud do for one
+ * slot (a copy of the mask - and of the whole camera-frame cloud - to the host, a synchronisation and a loop over every
+ * point on the CPU per getter) this does for all sequences with at most three launches, into DEVICE arrays of the caller,
+ * with no synchronisation: clouds and masks are read where they lie, no slot is involved, and the plane needs not be
+ * installed on one.
+ *
+ * mld_plane_inliers_create: an object bound to `ctx` (its stream, its device) for calls of n_seq (1 .. 65536) sequences
+ *   of up to max_points (1 .. 8 388 607) points each.  Of `params` only ransac_plane_use_camx_treshold and
+ *   ransac_plane_treshold_camx are read, and they are copied; T_cam_lidar (row-major 3x4): pass the values the context
+ *   was created with.  All memory is allocated here, none per call:
+ *     device  n_seq * (8 * ceil(max_points / 1024) + 56) bytes, and with the camx filter on
+ *             n_seq * 8 * ceil(max_points / 64) bytes more
+ *             (inlier and cloud count per 1024 points, descriptor; the filter's ballot per 64 points)
+ *     pinned  16 * 48 * n_seq bytes   (the descriptor ring)
+ *   The sizes are checked before the context is looked at, then the context, then params and T_cam_lidar.  Returns NULL on
+ *   failure with the reason in *status_out (optional) and the text in mld_plane_inliers_last_error(NULL).  Destroy the
+ *   object before its context.
+ *
+ * mld_plane_inliers_export_device: HOST tables of n_seq entries; every array they name is DEVICE memory.
+ *   pts_dev[s], n[s]    the cloud of sequence s: n[s] records of stride_bytes (16 or 32, x y z first), 4-byte aligned.
+ *                       0 <= n[s] <= max_points (beyond it: MLD_ERR_CAPACITY).
+ *   mask_dev[s]         ceil(n[s] / 32) uint32 words, 4-byte aligned (8-byte alignment is not needed): bit i of word
+ *                       i / 32 = point i is an inlier.  The bits at and beyond n[s] in the last word are IGNORED - a
+ *                       caller's own mask may carry anything there - and nothing beyond the last word is read.
+ *   Inlier r of a sequence is the r-th set bit in cloud order.  An inlier is IN THE CLOUD iff the filter is off or
+ *   fabs(x_cam) <= ransac_plane_treshold_camx; NaN fails.  Cloud point r is the r-th such inlier in cloud order.
+ *   counts_out_dev      required: ONE device array of n_seq records, 8-byte aligned.  Always complete, whatever the
+ *                       capacities and whichever outputs are null.
+ *   index_out[s]        capacity[s] int32: the original index of inlier r, ascending - bit for bit what
+ *                       mld_get_ground_plane_inliers lists on a slot that holds that cloud and mask.
+ *   lidar_out           optional (the table, or single entries): 3 x capacity[s] float32 column-major, the x, y, z of
+ *                       inlier r at [3 r], [3 r + 1], [3 r + 2]: the float bits of the record, copied.
+ *   cam_out             optional (the table, or single entries): 3 x capacity[s] float64 column-major, the camera-frame
+ *                       coordinates of cloud point r - bit for bit what mld_get_ground_plane_cloud writes, and what the
+ *                       cam_out rows of mld_projected_clouds_export_device hold at those indices (same transform,
+ *                       operation for operation).
+ *   capacity[s]         >= 0.  ONE capacity bounds each list by its own rank: the inlier rank for index_out and lidar_out,
+ *                       the cloud rank for cam_out.  Positions r >= capacity[s] are not written and nothing at or beyond
+ *                       min(count, capacity[s]) is touched; n_inliers > capacity[s] (n_cloud > capacity[s]) tells a
+ *                       truncated sequence.  capacity[s] = n[s] never truncates; capacity[s] == 0 needs none of the three
+ *                       arrays.
+ *   n[s] == 0 needs no cloud, mask or output array and gets a zero record.
+ *   Asynchronous on the context's stream: no synchronisation, no host read of device data, no runtime call per sequence,
+ *   nothing allocated per call.  The host tables are consumed before the call returns, so a caller may queue frames
+ *   ahead; the device arrays must stay valid until the work has run.  Like a context, the object serves one call at a
+ *   time.
+ *   MLD_ERR_INVALID_ARG with a text naming the function and the argument (mld_plane_inliers_last_error; "null object
+ *   (pi)" of NULL for a null object) on: a null object, a null table pts_dev, n, mask_dev, capacity or index_out, a null
+ *   counts_out_dev, a null cloud or mask of a sequence with points, a null index_out[s] where min(capacity[s], n[s]) > 0,
+ *   n[s] < 0, capacity[s] < 0, a stride other than 16 or 32, a cloud, mask, index_out or lidar_out array that is not
+ *   4-byte aligned, a cam_out array or counts_out_dev that is not 8-byte aligned.
+ */
+typedef struct mld_plane_inlier_counts {   /* 16 bytes */
+    int64_t n_inliers;   /* set mask bits below n[s]                       (getInlinersIndex().size()) */
+    int64_t n_cloud;     /* those that pass the camx filter; == n_inliers when the filter is off */
+} mld_plane_inlier_counts;
+
+typedef struct mld_plane_inliers mld_plane_inliers;
+mld_plane_inliers* mld_plane_inliers_create(mld_ctx* ctx, int n_seq, int64_t max_points, const mld_params* params,
+                                            const double T_cam_lidar[12], int* status_out);
+void mld_plane_inliers_destroy(mld_plane_inliers* pi);
+const char* mld_plane_inliers_last_error(const mld_plane_inliers* pi);
+int mld_plane_inliers_export_device(mld_plane_inliers* pi, const void* const* pts_dev, const int64_t* n, int stride_bytes,
+                                    const uint32_t* const* mask_dev, const int64_t* capacity,
+                                    mld_plane_inlier_counts* counts_out_dev, int32_t* const* index_out,
+                                    float* const* lidar_out, double* const* cam_out);
+
+/*
  * Debug / parity getters (host buffers; each synchronises).
  *   mld_get_visible_count           -> _points_cs_image_visible.cols()         (DepthEstimator.cpp:192)
  *   mld_get_visible_image_points    -> getPointsCloudImageCs, 2 x Nvis col-major (:392-394)

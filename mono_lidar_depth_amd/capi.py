@@ -144,6 +144,11 @@ class MldDepthReport(C.Structure):
     _fields_ = [("counts", C.c_int64 * MLD_RESULT_TYPE_COUNT), ("other", C.c_int64), ("point_count", C.c_int64), ("n_interpolated", C.c_int64)]
 
 
+class MldPlaneInlierCounts(C.Structure):
+    """mld_plane_inlier_counts (include/mld.h): one sequence of mld_plane_inliers_export_device, 16 bytes = 2 int64."""
+    _fields_ = [("n_inliers", C.c_int64), ("n_cloud", C.c_int64)]
+
+
 # Every symbol include/mld.h declares: (name, restype, argtypes)
 _P = C.POINTER
 _SIGNATURES = [
@@ -244,6 +249,11 @@ _SIGNATURES = [
      [C.c_void_p] + [_P(C.c_void_p)] * 2),
     ("mld_depth_reports_collect_tracks_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 4 + [_P(C.c_int64)] * 2 +
      [C.c_void_p] + [_P(C.c_void_p)] * 2),
+    ("mld_plane_inliers_create", C.c_void_p, [C.c_void_p, C.c_int, C.c_int64, _P(MldParams), _P(C.c_double), _P(C.c_int)]),
+    ("mld_plane_inliers_destroy", None, [C.c_void_p]),
+    ("mld_plane_inliers_last_error", C.c_char_p, [C.c_void_p]),
+    ("mld_plane_inliers_export_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64), C.c_int, _P(C.c_void_p),
+                                                  _P(C.c_int64), C.c_void_p] + [_P(C.c_void_p)] * 3),
     ("mld_get_visible_count", C.c_int, [C.c_void_p, C.c_int, _P(C.c_int64)]),
     ("mld_get_visible_image_points", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
     ("mld_get_point_index", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),

@@ -17,7 +17,8 @@ majority vote in a window of a label image (matches_conversion_ros_tool, semanti
 sequences of a batch in one call and ahead of the projection.  ProjectedClouds (mld_projected_clouds_*) is the frame's
 PointcloudData - visible list, point index, camera-frame cloud, pixel map - of all sequences as device tensors.
 DepthReports (mld_depth_reports_*) is the depth-calculation statistics (getDepthCalcStats) and the interpolated cloud
-(getCloudInterpolated) of all sequences, from device tensors into device tensors.
+(getCloudInterpolated) of all sequences, from device tensors into device tensors.  PlaneInliers (mld_plane_inliers_*) is
+the inlier index list, lidar-frame matrix and camera-frame cloud of the ground planes of all sequences, from their masks.
 """
 from __future__ import annotations
 
@@ -167,7 +168,7 @@ class TrackletDepthModule:
 
 
 class _BatchObject:
-    """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes, ProjectedClouds and DepthReports share: an object of the C-ABI (mld_<_NAME>_create /
+    """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes, ProjectedClouds, DepthReports and PlaneInliers share: an object of the C-ABI (mld_<_NAME>_create /
     _destroy / _last_error) on an estimator's context, its handle in the attribute named _HANDLE, and the tensors of
     the calls that may still be queued."""
 
@@ -602,6 +603,80 @@ class DepthReports(_BatchObject):
                     list(points) if points is not None else None, list(feature) if feature is not None else None))
 
 
+class PlaneInliers(_BatchObject):
+    """What the reference keeps on a frame's ground plane besides the coefficients, for S sequences per call
+    (mld_plane_inliers_*, include/mld.h), from the inlier bitmasks SemanticPlanes / RansacPlanes write: per sequence the
+    ascending inlier indices (GroundPlane::getInlinersIndex), the lidar-frame float matrix of the inliers
+    (getMatrixFromIndices) and the camera-frame inlier cloud filtered by ransac_plane_use_camx_treshold /
+    ransac_plane_treshold_camx (getCloudRansacPlane) - bit for bit what getGroundPlaneInliers / getCloudRansacPlane give
+    on a slot that holds that cloud and mask, without a frame slot and into device tensors.  `parameters` (default: the
+    estimator's) is copied at creation.  Lists of S torch CUDA tensors in and out; asynchronous on the estimator's
+    stream.  Close it before its estimator."""
+
+    _NAME, _HANDLE = "plane_inliers", "_pi"
+
+    def __init__(self, estimator: DepthEstimator, n_seq: int, max_points: int, parameters=None):
+        self.S, self.max_points = int(n_seq), int(max_points)
+        P = parameters if parameters is not None else estimator.getParameters()
+        T = np.ascontiguousarray(np.asarray(estimator._T, dtype=np.float64).reshape(-1)[:12])
+        self._create(estimator, self.S, self.max_points, C.byref(P), T.ctypes.data_as(C.POINTER(C.c_double)))
+
+    @staticmethod
+    def mask_words(n_points: int) -> int:
+        """32-bit words of the inlier mask of a cloud of n_points."""
+        return (int(n_points) + 31) // 32
+
+    def export(self, clouds, masks, capacity, counts, index, lidar=None, cam=None):
+        """clouds: S contiguous float32 CUDA tensors [n, 4] or [n, 8] of one width (an entry None: a sequence without
+        points); masks: S int32 CUDA tensors of at least mask_words(n) entries (None where the cloud is); capacity: S
+        integers, or None (= n, never truncated); counts: an int64 CUDA tensor [S, 2] that receives (n_inliers, n_cloud);
+        index: S int32 CUDA tensors of at least min(capacity, n) entries; lidar: None, or S float32 CUDA tensors of 3 *
+        min(capacity, n) entries (a contiguous [capacity, 3]); cam: None, or S float64 CUDA tensors of that length.
+        Single entries of index may be None where min(capacity, n) is 0, of lidar and cam anywhere.  Inliers (cloud
+        points) at or beyond a sequence's capacity are dropped, which the caller sees from the counts."""
+        S = self.S
+        for name, ts in (("clouds", clouds), ("masks", masks), ("capacity", capacity), ("index", index), ("lidar", lidar),
+                         ("cam", cam)):
+            if ts is not None and len(ts) != S:
+                raise ValueError(f"{name}: expected {S} entries, one per sequence")
+        if tuple(counts.shape) != (S, 2) or counts.element_size() != 8 or not counts.is_contiguous():
+            raise ValueError(f"counts must be a contiguous int64 tensor [{S}, 2]")
+        width = next((int(cl.shape[1]) for cl in clouds if cl is not None), 4)
+        ns, caps = [], []
+
+        def holds(ts, s, entries, size, name, required):
+            t = ts[s] if ts is not None else None
+            if t is None:
+                if required and entries:
+                    raise ValueError(f"sequence {s}: {name} is missing")
+                return
+            if t.element_size() != size or not t.is_contiguous() or int(t.numel()) < entries:
+                raise ValueError(f"sequence {s}: {name} must be contiguous, of {size}-byte elements, at least {entries} of them")
+
+        for s, cl in enumerate(clouds):
+            n = 0
+            if cl is not None:
+                if cl.dim() != 2 or int(cl.shape[1]) != width or width not in (4, 8) or not cl.is_contiguous() or cl.element_size() != 4:
+                    raise ValueError("clouds: contiguous float32 [n, 4] or [n, 8], one width for all sequences")
+                n = int(cl.shape[0])
+            cap = n if capacity is None else int(capacity[s])
+            if cap < 0:
+                raise ValueError(f"sequence {s}: negative capacity")
+            ns.append(n)
+            caps.append(cap)
+            m = min(cap, n)
+            holds(masks, s, self.mask_words(n), 4, "masks", True)
+            holds(index, s, m, 4, "index", True)
+            holds(lidar, s, 3 * m, 4, "lidar", False)
+            holds(cam, s, 3 * m, 8, "cam", False)
+        vp = self._ptrs
+        self._check(self._lib.mld_plane_inliers_export_device(
+            self._pi, vp(clouds), (C.c_int64 * S)(*ns), 4 * width, vp(masks), (C.c_int64 * S)(*caps), int(counts.data_ptr()),
+            vp(index), vp(lidar) if lidar is not None else None, vp(cam) if cam is not None else None))
+        self._hold((list(clouds), list(masks), counts, list(index), list(lidar) if lidar is not None else None,
+                    list(cam) if cam is not None else None))
+
+
 class TrackletBatch:
     """The tracklet layer for S independent sequences at once (mld_set_clouds_planes_range_device +
     mld_tracklets_depths_device): the estimator's frame slots are two banks of S slots, sequence s keeps its current
@@ -627,6 +702,7 @@ class TrackletBatch:
         self.rplanes: Optional[RansacPlanes] = None
         self.pclouds: Optional[ProjectedClouds] = None
         self.depth_reports: Optional[DepthReports] = None
+        self.inliers: Optional[PlaneInliers] = None
 
     def attach_planes(self, max_points: int = 1 << 19) -> SemanticPlanes:
         """The semantic ground plane estimator of the S sequences that semantic_planes() runs ahead of a step, for clouds
@@ -719,6 +795,38 @@ class TrackletBatch:
                "pixel_map": [torch.empty((pc.height, pc.width), dtype=torch.int32, device=dev) for _ in ns] if pixel_map else None}
         self.est._after_torch(*[c for c in clouds if c is not None][:1])
         pc.export(clouds, caps, out["n_visible"], out["uv"], out["index"], out["depth"], out["cam"], out["pixel_map"])
+        self.est.orderTorchAfter()
+        return out
+
+    def attach_plane_inliers(self, max_points: int = 1 << 19) -> PlaneInliers:
+        """The export of the ground-plane inliers of the S sequences that plane_inliers() runs, for clouds of up to
+        max_points points (default: 128 beams x 4096, 4 KB of scratch per sequence, 68 KB with the camx filter on).  It
+        takes the estimator's parameters as they are now."""
+        if self.inliers is None:
+            self.inliers = PlaneInliers(self.est, self.S, max_points)
+        return self.inliers
+
+    def plane_inliers(self, clouds, masks, lidar: bool = False, cam: bool = False, capacity=None):
+        """The inliers of this frame's ground planes as device tensors, from the masks exactly as semantic_planes() /
+        ransac_planes() return them: returns a dict with counts (int64 [S, 2] = (n_inliers, n_cloud)), index (S int32
+        [capacity]: GroundPlane::getInlinersIndex) and, where asked for, lidar (S float32 [capacity, 3]:
+        getMatrixFromIndices) and cam (S float64 [capacity, 3]: getCloudRansacPlane, filtered by
+        ransac_plane_use_camx_treshold / ransac_plane_treshold_camx); the rows at and beyond the counts are not written.
+        capacity: S integers, or None (= n, never truncated).  One call on the GPU and no synchronisation: torch's
+        current stream is made to wait for the export, so torch operations may consume the tensors at once; a host read
+        synchronises as usual.  attach_plane_inliers() first."""
+        import torch
+        if self.inliers is None:
+            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.plane_inliers without attach_plane_inliers")
+        dev = next((c.device for c in clouds if c is not None), torch.device("cuda", self.est._device))
+        ns = [int(c.shape[0]) if c is not None else 0 for c in clouds]
+        caps = [min(int(capacity[s]), ns[s]) if capacity is not None else ns[s] for s in range(self.S)]
+        out = {"counts": torch.empty((self.S, 2), dtype=torch.int64, device=dev),
+               "index": [torch.empty(m, dtype=torch.int32, device=dev) for m in caps],
+               "lidar": [torch.empty((m, 3), dtype=torch.float32, device=dev) for m in caps] if lidar else None,
+               "cam": [torch.empty((m, 3), dtype=torch.float64, device=dev) for m in caps] if cam else None}
+        self.est._after_torch(*[c for c in clouds if c is not None][:1])
+        self.inliers.export(clouds, masks, caps, out["counts"], out["index"], out["lidar"], out["cam"])
         self.est.orderTorchAfter()
         return out
 
@@ -876,4 +984,7 @@ class TrackletBatch:
         if self.depth_reports is not None:
             self.depth_reports.close()
             self.depth_reports = None
+        if self.inliers is not None:
+            self.inliers.close()
+            self.inliers = None
         self.est.close()
