@@ -986,6 +986,130 @@ int mld_plane_inliers_export_device(mld_plane_inliers* pi, const void* const* pt
                                     float* const* lidar_out, double* const* cam_out);
 
 /*
+ * Per-feature traces of a batch — why a feature got the depth it got, for n_seq independent sequences in one call:
+ *   the triangle corners     getCloudTriangleCorners / ActivateDebugMode (DepthEstimator.cpp:348-350,
+ *                            PlaneEstimationCalcMaxSpanningTriangle.cpp:20-35)
+ *   the per-feature record   DepthCalcStatsSinglePoint (do_debug_singleFeatures, DepthCalcStatsSinglePoint.h:20-67): the
+ *                            neighbours, the segmented points, the histogram borders and the plane
+ * What mld_calculate_depth_debug does for one slot (features from the host, every feature through the wave-cooperative
+ * depth kernel, nine corner coordinates back to the host) this does for all sequences with two launches, into DEVICE
+ * arrays of the caller, with no synchronisation and without a frame slot.  It re-walks the STRUCTURAL part of the
+ * per-feature path on the arrays mld_projected_clouds_export_device writes, plus (optionally) the plane that
+ * mld_semantic_planes / mld_ransac_planes leave on the device, operation for operation as the depth path does; integers
+ * and float bits of a record equal what that path worked with.  Stages traced:
+ *   1. the 1.0 x 1.0 window (NeighborFinderPixel.cpp:60-95): half sizes and clamping in f64, (int) truncation of the
+ *      bounds.  A non-finite u or v gives an empty window and sets MLD_TRACE_FLAG_NONFINITE_FEATURE.
+ *      n_nb < radiusSearch_count_min (compared as unsigned): main_type 2, the road is not reached.
+ *   2. the histogram segmentation (HistogramPointDepth.cpp:15-123) including its lastBinValue early return; with
+ *      do_use_histogram_segmentation off every neighbour is kept.
+ *   3. the corners: the farthest pair with strict '>' (the first pair in (i, j) order wins), the third corner (the last
+ *      point is never one); with do_use_triangle_size_maximation off the first three points.  Then the planarity test, the
+ *      viewing ray through Kinv with the flip, Hyperplane::Through with its degenerate fallback, the orthogonality test,
+ *      the global and local thresholds and cut-behind-camera.  main_type / main_depth are the result of this main path.
+ *   4. the road fallback, when the sequence has a plane, do_use_ransac_plane is on and main_type is neither 1 nor 2: the
+ *      2.0 x 1.5 window, the f32 un-normalised point-to-plane distance after the f64 camera->lidar transform, the mask
+ *      bit of the original index.  The road fit itself is NOT repeated.  road_state says where the path ended:
+ *        MLD_TRACE_ROAD_FAR_NEIGHBOUR   a neighbour farther than ransac_plane_point_distance_treshold: the final type is
+ *                                       main_type, the final depth -1; n_road_inl is 0 and no inlier list is written
+ *                                       (the reference leaves at that neighbour)
+ *        MLD_TRACE_ROAD_FEW_INLIERS     fewer than three inliers: the final type is main_type, the final depth -1
+ *        MLD_TRACE_ROAD_FIT             the estimator ran: type and depth are whatever the depth call returned
+ *        MLD_TRACE_ROAD_FEW_NEIGHBOURS  n_road < radiusSearch_count_min, evaluated as the reference evaluates it
+ *                                       (DepthEstimator.cpp:585-586).  It cannot occur: the wide window contains the
+ *                                       narrow one, whose count has passed the same test.
+ *
+ * mld_feature_traces_create: an object bound to `ctx` (its stream, its device) for calls of n_seq (1 .. 65536) sequences
+ *   of up to max_features (1 .. 16 777 216) features each.  params, camera and T_cam_lidar (row-major 3x4) are copied:
+ *   pass the values the context was created with.  All memory is allocated here, none per call:
+ *     device  120 * n_seq bytes        (the descriptors)
+ *     pinned  16 * 120 * n_seq bytes   (the descriptor ring)
+ *   The sizes are checked before the context is looked at, then the context, then params, camera and T_cam_lidar (null),
+ *   and then, still without a use of the context:
+ *     MLD_ERR_UNSUPPORTED_MODE  do_use_PCA (the eigen-solve is a tolerance path, the trace promises equality)
+ *     the refusals of mld_create for a parameter set, a camera and a transform, with its status codes
+ *     MLD_ERR_CAPACITY          a wide window that can cover more than 1024 cells, counted as
+ *                               min(W, floor(2 halfX2) + 2) * min(H, floor(2 halfY2) + 2) with halfX2 =
+ *                               pixelarea_search_witdh * 0.5 * 2.0 and halfY2 = pixelarea_search_height * 0.5 * 1.5
+ *                               (C0: 14 x 15 = 210)
+ *   Returns NULL on failure with the reason in *status_out (optional) and the text in
+ *   mld_feature_traces_last_error(NULL).  Destroy the object before its context.
+ *
+ * mld_feature_traces_collect_device (DepthEstimator layer: uv[s] 2 x n_features[s] f64 column-major) and
+ * mld_feature_traces_collect_tracks_device (tracklet layer: u[s], v[s] f32; u = (double)truncf(u), likewise v, exactly as
+ * mld_depth_reports_collect_tracks_device): HOST tables of n_seq entries, consumed before the call returns; every array
+ * they name is DEVICE memory, naturally aligned for its element type (the records: 8 bytes).
+ *   n_features[s]       0 <= n_features[s] <= max_features (beyond it: MLD_ERR_CAPACITY).  A sequence with 0 features
+ *                       needs no arrays.
+ *   map[s]              W * H int32, index x + y * W: the visible index, or -1
+ *   index[s], index_len[s]   _pointIndex: the original index of visible point r, index_len[s] entries
+ *   cam[s], n_points[s] 3 x n_points[s] f64 column-major, the camera-frame cloud
+ *                       All three exactly as mld_projected_clouds_export_device wrote them for that cloud (pixel_map_out,
+ *                       index_out with a capacity that did not truncate, cam_out); n_points[s], index_len[s] <= 8 388 607.
+ *   coeffs, mask_dev    as mld_set_clouds_planes_range_device takes them (n_seq x 4 floats on the HOST; a host table of
+ *                       device bitmasks of ceil(n_points[s] / 32) words), both or neither.  A NULL mask_dev[s]: sequence s
+ *                       has no plane (the reference's ransacPlane == nullptr).
+ *   trace_out[s]        n_features[s] records; every record is written completely on every call.
+ *   nb_out, seg_out, road_out, road_inl_out   optional (the table, or single entries): list_capacity x n_features[s] int32
+ *                       each, feature i's row at i * list_capacity.
+ *                         nb_out        visible indices of the narrow window's neighbours, in the reference's row-major
+ *                                       scan order
+ *                         seg_out       positions into that list of the neighbours the segmentation kept
+ *                         road_out      visible indices of the wide window's neighbours
+ *                         road_inl_out  positions into that list of the plane inliers
+ *                       The first min(count, list_capacity) entries of a row are written and nothing behind them is
+ *                       touched; the counts of the record are always complete, so a truncated row shows.
+ *   list_capacity       0 .. 1024; with 0 no list array is needed or written.
+ *   Robustness: a map value other than -1 outside [0, index_len[s]) and an index value outside [0, n_points[s]) make the
+ *   cell count as EMPTY and set MLD_TRACE_FLAG_BAD_INPUT on the features whose scanned windows met it; no read leaves the
+ *   arrays as the host tables size them.
+ *   Asynchronous on the context's stream: no synchronisation, no host read of device data, no runtime call per sequence,
+ *   nothing allocated per call, at most two launches (the descriptor upload and k_feature_trace, one wavefront per
+ *   feature).  The device arrays must stay valid until the work has run.  Like a context, the object serves one call at a
+ *   time.
+ *   MLD_ERR_INVALID_ARG with a text naming the function and the argument (mld_feature_traces_last_error; "null object
+ *   (ft)" of NULL for a null object) on: a null object, a null table uv / u / v, n_features, map, index, index_len, cam,
+ *   n_points or trace_out, a null uv / u / v, map or trace_out array of a sequence with features (index, cam: where
+ *   index_len[s], n_points[s] > 0), a negative count, list_capacity outside 0 .. 1024, coeffs without mask_dev or the
+ *   other way round, an int32 or float array that is not 4-byte aligned, an f64 array or trace_out that is not 8-byte
+ *   aligned.
+ */
+enum { MLD_TRACE_ROAD_NOT_REACHED = 0, MLD_TRACE_ROAD_FEW_NEIGHBOURS = 1, MLD_TRACE_ROAD_FAR_NEIGHBOUR = 2,
+       MLD_TRACE_ROAD_FEW_INLIERS = 3, MLD_TRACE_ROAD_FIT = 4 };
+enum { MLD_TRACE_FLAG_BAD_INPUT = 1, MLD_TRACE_FLAG_NONFINITE_FEATURE = 2 };
+
+typedef struct mld_feature_trace {      /* 184 bytes, 8-byte aligned */
+    int32_t main_type;      /* DepthResultType at the end of the main path (DepthEstimator.cpp:509-577) */
+    int32_t road_state;     /* MLD_TRACE_ROAD_* */
+    int32_t n_nb, n_seg;    /* neighbours of the 1.0 x 1.0 window; those the segmentation kept (0 if it failed) */
+    int32_t n_road, n_road_inl; /* neighbours of the 2.0 x 1.5 window; plane inliers among them */
+    int32_t corner_pos[3];  /* positions into the segmented list, -1 without corners */
+    int32_t corner_vis[3];  /* their visible indices, -1 */
+    int32_t flags, pad_;
+    double  main_depth;     /* depth at the end of the main path: -1 unless main_type == MLD_Success */
+    double  hist_lower, hist_higher;  /* borders of the chosen bin (HistogramPointDepth.cpp:99-100), -1 without one */
+    double  plane_n[3], plane_offset; /* Hyperplane::Through of the corners; NaN unless the plane was formed */
+    double  corners[9];     /* camera-frame corner1, corner2, corner3 (getCloudTriangleCorners); NaN without corners */
+} mld_feature_trace;
+
+typedef struct mld_feature_traces mld_feature_traces;
+mld_feature_traces* mld_feature_traces_create(mld_ctx* ctx, int n_seq, int64_t max_features, const mld_params* params,
+                                              const mld_camera* camera, const double T_cam_lidar[12], int* status_out);
+void mld_feature_traces_destroy(mld_feature_traces* ft);
+const char* mld_feature_traces_last_error(const mld_feature_traces* ft);
+int mld_feature_traces_collect_device(mld_feature_traces* ft, const double* const* uv, const int64_t* n_features,
+                                      const int32_t* const* map, const int32_t* const* index, const int64_t* index_len,
+                                      const double* const* cam, const int64_t* n_points, const float* coeffs,
+                                      const uint32_t* const* mask_dev, int list_capacity, mld_feature_trace* const* trace_out,
+                                      int32_t* const* nb_out, int32_t* const* seg_out, int32_t* const* road_out,
+                                      int32_t* const* road_inl_out);
+int mld_feature_traces_collect_tracks_device(mld_feature_traces* ft, const float* const* u, const float* const* v,
+                                             const int64_t* n_features, const int32_t* const* map, const int32_t* const* index,
+                                             const int64_t* index_len, const double* const* cam, const int64_t* n_points,
+                                             const float* coeffs, const uint32_t* const* mask_dev, int list_capacity,
+                                             mld_feature_trace* const* trace_out, int32_t* const* nb_out, int32_t* const* seg_out,
+                                             int32_t* const* road_out, int32_t* const* road_inl_out);
+
+/*
  * Debug / parity getters (host buffers; each synchronises).
  *   mld_get_visible_count           -> _points_cs_image_visible.cols()         (DepthEstimator.cpp:192)
  *   mld_get_visible_image_points    -> getPointsCloudImageCs, 2 x Nvis col-major (:392-394)

@@ -149,6 +149,21 @@ class MldPlaneInlierCounts(C.Structure):
     _fields_ = [("n_inliers", C.c_int64), ("n_cloud", C.c_int64)]
 
 
+# mld_feature_trace::road_state and ::flags (include/mld.h)
+MLD_TRACE_ROAD_NOT_REACHED, MLD_TRACE_ROAD_FEW_NEIGHBOURS, MLD_TRACE_ROAD_FAR_NEIGHBOUR = 0, 1, 2
+MLD_TRACE_ROAD_FEW_INLIERS, MLD_TRACE_ROAD_FIT = 3, 4
+MLD_TRACE_FLAG_BAD_INPUT, MLD_TRACE_FLAG_NONFINITE_FEATURE = 1, 2
+
+
+class MldFeatureTrace(C.Structure):
+    """mld_feature_trace (include/mld.h): one feature of mld_feature_traces_collect_*_device, 184 bytes."""
+    _fields_ = [("main_type", C.c_int32), ("road_state", C.c_int32), ("n_nb", C.c_int32), ("n_seg", C.c_int32),
+                ("n_road", C.c_int32), ("n_road_inl", C.c_int32), ("corner_pos", C.c_int32 * 3), ("corner_vis", C.c_int32 * 3),
+                ("flags", C.c_int32), ("pad_", C.c_int32), ("main_depth", C.c_double), ("hist_lower", C.c_double),
+                ("hist_higher", C.c_double), ("plane_n", C.c_double * 3), ("plane_offset", C.c_double),
+                ("corners", C.c_double * 9)]
+
+
 # Every symbol include/mld.h declares: (name, restype, argtypes)
 _P = C.POINTER
 _SIGNATURES = [
@@ -254,6 +269,15 @@ _SIGNATURES = [
     ("mld_plane_inliers_last_error", C.c_char_p, [C.c_void_p]),
     ("mld_plane_inliers_export_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64), C.c_int, _P(C.c_void_p),
                                                   _P(C.c_int64), C.c_void_p] + [_P(C.c_void_p)] * 3),
+    ("mld_feature_traces_create", C.c_void_p, [C.c_void_p, C.c_int, C.c_int64, _P(MldParams), _P(MldCamera), _P(C.c_double),
+                                               _P(C.c_int)]),
+    ("mld_feature_traces_destroy", None, [C.c_void_p]),
+    ("mld_feature_traces_last_error", C.c_char_p, [C.c_void_p]),
+    ("mld_feature_traces_collect_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)] + [_P(C.c_void_p)] * 2 +
+     [_P(C.c_int64), _P(C.c_void_p), _P(C.c_int64), _P(C.c_float), _P(C.c_void_p), C.c_int] + [_P(C.c_void_p)] * 5),
+    ("mld_feature_traces_collect_tracks_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 2 + [_P(C.c_int64)] +
+     [_P(C.c_void_p)] * 2 + [_P(C.c_int64), _P(C.c_void_p), _P(C.c_int64), _P(C.c_float), _P(C.c_void_p), C.c_int] +
+     [_P(C.c_void_p)] * 5),
     ("mld_get_visible_count", C.c_int, [C.c_void_p, C.c_int, _P(C.c_int64)]),
     ("mld_get_visible_image_points", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
     ("mld_get_point_index", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),

@@ -1,6 +1,6 @@
 // mld_batch_object.h — what the batch objects on top of the public C-ABI have in common (mld_tracks, mld_labels,
-// mld_semantic_planes, mld_ransac_planes, mld_projected_clouds, mld_depth_reports, mld_plane_inliers; each a translation
-// unit of its own that includes this header and include/mld.h only):
+// mld_semantic_planes, mld_ransac_planes, mld_projected_clouds, mld_depth_reports, mld_plane_inliers, mld_feature_traces;
+// each a translation unit of its own that includes this header and include/mld.h only):
 //   Object         the fields every object has (context, stream, device, last error), fail() and the MLD_HIP check on them
 //   DescRing<D>    the per-call table of n_seq descriptors: staged on the host, copied into one of kGens pinned
 //                  generations and moved to device memory by a kernel on the object's stream

@@ -168,7 +168,7 @@ class TrackletDepthModule:
 
 
 class _BatchObject:
-    """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes, ProjectedClouds, DepthReports and PlaneInliers share: an object of the C-ABI (mld_<_NAME>_create /
+    """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes, ProjectedClouds, DepthReports, PlaneInliers and FeatureTraces share: an object of the C-ABI (mld_<_NAME>_create /
     _destroy / _last_error) on an estimator's context, its handle in the attribute named _HANDLE, and the tensors of
     the calls that may still be queued."""
 
@@ -677,6 +677,118 @@ class PlaneInliers(_BatchObject):
                     list(cam) if cam is not None else None))
 
 
+class FeatureTraces(_BatchObject):
+    """Why a feature got the depth it got, for S sequences per call (mld_feature_traces_*, include/mld.h): per feature
+    the record the reference calls DepthCalcStatsSinglePoint - neighbour and segmented counts, histogram borders, corner
+    positions, the plane - with the triangle corners of getCloudTriangleCorners and the state the road fallback ended in,
+    and, where asked for, the index lists behind the counts.  It runs on the tensors ProjectedClouds.export wrote
+    (pixel_map, index, cam) and on the planes as prepare() / prepare_step() take them.  collect() takes float64 uv,
+    collect_tracks() the float32 u, v of the tracklet layer (truncated to the integer pixel).  `parameters` (default: the
+    estimator's) is copied at creation; do_use_PCA is refused.  Lists of S torch CUDA tensors in and out; asynchronous on
+    the estimator's stream.  Close it before its estimator."""
+
+    _NAME, _HANDLE = "feature_traces", "_ft"
+    WORDS = 23  # int64 words of a record (capi.MldFeatureTrace, 184 bytes)
+    DTYPE = np.dtype(capi.MldFeatureTrace)
+    MAX_LIST = 1024
+
+    def __init__(self, estimator: DepthEstimator, n_seq: int, max_features: int, parameters=None):
+        self.S, self.max_features = int(n_seq), int(max_features)
+        P = parameters if parameters is not None else estimator.getParameters()
+        cam = estimator._camera.as_struct()
+        self.width, self.height = int(cam.width), int(cam.height)
+        T = np.ascontiguousarray(np.asarray(estimator._T, dtype=np.float64).reshape(-1)[:12])
+        self._create(estimator, self.S, self.max_features, C.byref(P), C.byref(cam), T.ctypes.data_as(C.POINTER(C.c_double)))
+
+    @classmethod
+    def records(cls, trace) -> np.ndarray:
+        """A trace tensor (int64 [n, 23]) as a NumPy record array with the fields of capi.MldFeatureTrace (copies to
+        the host, which synchronises as usual)."""
+        return np.ascontiguousarray(trace.cpu().numpy()).reshape(-1).view(cls.DTYPE)
+
+    def _collect(self, ns, feats, maps, index, cam, trace, coeffs, masks, list_capacity, lists):
+        S, cap = self.S, int(list_capacity)
+        names = ("nb", "seg", "road", "road_inl")
+        for name, ts in (("pixel_map", maps), ("index", index), ("cam", cam), ("trace", trace), ("masks", masks)) + tuple(zip(names, lists)):
+            if ts is not None and len(ts) != S:
+                raise ValueError(f"{name}: expected {S} entries, one per sequence")
+        if not 0 <= cap <= self.MAX_LIST:
+            raise ValueError(f"list_capacity must be in 0 .. {self.MAX_LIST}")
+        if (coeffs is None) != (masks is None):
+            raise ValueError("coeffs and masks come together or not at all")
+
+        def holds(t, s, entries, size, name):
+            if t is None:
+                raise ValueError(f"sequence {s}: {name} is missing")
+            if t.element_size() != size or not t.is_contiguous() or int(t.numel()) < entries:
+                raise ValueError(f"sequence {s}: {name} must be contiguous, of {size}-byte elements, at least {entries} of them")
+
+        n_idx, n_pts = [], []
+        for s, n in enumerate(ns):
+            n_idx.append(int(index[s].numel()) if index[s] is not None else 0)
+            n_pts.append(int(cam[s].numel()) // 3 if cam[s] is not None else 0)
+            if n == 0:
+                continue
+            holds(maps[s], s, self.width * self.height, 4, "pixel_map")
+            if index[s] is not None:
+                holds(index[s], s, 0, 4, "index")
+            if cam[s] is not None:
+                holds(cam[s], s, 0, 8, "cam")
+            holds(trace[s], s, self.WORDS * n, 8, "trace")
+            for name, ts in zip(names, lists):
+                if cap and ts is not None and ts[s] is not None:
+                    holds(ts[s], s, cap * n, 4, name)
+        co = None
+        if coeffs is not None:
+            co = np.ascontiguousarray(coeffs, dtype=np.float32).reshape(S, 4)
+        vp = self._ptrs
+        tail = (vp(maps), vp(index), (C.c_int64 * S)(*n_idx), vp(cam), (C.c_int64 * S)(*n_pts),
+                co.ctypes.data_as(C.POINTER(C.c_float)) if co is not None else None, vp(masks) if masks is not None else None,
+                cap, vp(trace)) + tuple(vp(ts) if ts is not None else None for ts in lists)
+        nf = (C.c_int64 * S)(*ns)
+        if len(feats) == 1:
+            rc = self._lib.mld_feature_traces_collect_device(self._ft, vp(feats[0]), nf, *tail)
+        else:
+            rc = self._lib.mld_feature_traces_collect_tracks_device(self._ft, vp(feats[0]), vp(feats[1]), nf, *tail)
+        self._check(rc)
+        self._hold(([list(t) for t in feats], list(maps), list(index), list(cam), list(trace),
+                    list(masks) if masks is not None else None, [list(ts) if ts is not None else None for ts in lists]))
+
+    def collect(self, uv, pixel_map, index, cam, trace, coeffs=None, masks=None, list_capacity: int = 0, nb=None, seg=None,
+                road=None, road_inl=None):
+        """uv: S contiguous float64 CUDA tensors [n, 2] (an entry None: a sequence without features); pixel_map, index,
+        cam: the S tensors each that ProjectedClouds.export wrote for the clouds (int32 [height, width], int32 of a
+        capacity that did not truncate, float64 [points, 3]); trace: S int64 CUDA tensors of at least 23 * n entries (a
+        contiguous [n, 23]: capi.MldFeatureTrace, see records()); coeffs (float32 [S, 4], host) and masks (S int32 CUDA
+        tensors, an entry None: that sequence has no plane): both or neither; nb, seg, road, road_inl: None, or S int32
+        CUDA tensors of at least list_capacity * n entries (a contiguous [n, list_capacity]; single entries may be None).
+        A row receives the first min(count, list_capacity) entries of its list; the counts of the record are complete."""
+        if len(uv) != self.S:
+            raise ValueError(f"uv: expected {self.S} entries, one per sequence")
+        ns = []
+        for s, t in enumerate(uv):
+            if t is not None and (t.element_size() != 8 or not t.is_contiguous() or int(t.numel()) % 2):
+                raise ValueError(f"sequence {s}: uv must be a contiguous float64 tensor [n, 2]")
+            ns.append(int(t.numel()) // 2 if t is not None else 0)
+        self._collect(ns, (uv,), pixel_map, index, cam, trace, coeffs, masks, list_capacity, (nb, seg, road, road_inl))
+
+    def collect_tracks(self, u, v, pixel_map, index, cam, trace, coeffs=None, masks=None, list_capacity: int = 0, nb=None,
+                       seg=None, road=None, road_inl=None):
+        """As collect(), on the tensors of TrackletBatch.prepare_step() / prepare(): u, v (u_new, v_new): S float32 CUDA
+        tensors [n]."""
+        if len(u) != self.S or len(v) != self.S:
+            raise ValueError(f"u, v: expected {self.S} entries, one per sequence")
+        ns = []
+        for s, (a, b) in enumerate(zip(u, v)):
+            if (a is None) != (b is None):
+                raise ValueError(f"sequence {s}: u and v come together")
+            for t in (a, b):
+                if t is not None and (t.element_size() != 4 or not t.is_contiguous() or int(t.numel()) != int(a.numel())):
+                    raise ValueError(f"sequence {s}: u and v must be contiguous float32 tensors of one length")
+            ns.append(int(a.numel()) if a is not None else 0)
+        self._collect(ns, (u, v), pixel_map, index, cam, trace, coeffs, masks, list_capacity, (nb, seg, road, road_inl))
+
+
 class TrackletBatch:
     """The tracklet layer for S independent sequences at once (mld_set_clouds_planes_range_device +
     mld_tracklets_depths_device): the estimator's frame slots are two banks of S slots, sequence s keeps its current
@@ -703,6 +815,7 @@ class TrackletBatch:
         self.pclouds: Optional[ProjectedClouds] = None
         self.depth_reports: Optional[DepthReports] = None
         self.inliers: Optional[PlaneInliers] = None
+        self.feature_traces: Optional[FeatureTraces] = None
 
     def attach_planes(self, max_points: int = 1 << 19) -> SemanticPlanes:
         """The semantic ground plane estimator of the S sequences that semantic_planes() runs ahead of a step, for clouds
@@ -864,6 +977,42 @@ class TrackletBatch:
         self.est.orderTorchAfter()
         return out
 
+    def attach_traces(self) -> FeatureTraces:
+        """The per-feature traces of the S sequences that traces() runs, for up to max_tracks tracks per sequence.  It
+        takes the estimator's parameters as they are now."""
+        if self.feature_traces is None:
+            self.feature_traces = FeatureTraces(self.est, self.S, self.max_tracks)
+        return self.feature_traces
+
+    def traces(self, f, clouds, list_capacity: int = 0, planes: bool = True):
+        """Why the tracks of table `f` (prepare_step() / prepare()) got their depths on this frame's clouds:
+        FeatureTraces.collect_tracks on the table's u_new, v_new, its planes and masks (planes=False: traced without a
+        plane) and on `clouds`, the dict projected_clouds(cam=True, pixel_map=True) returned for the same clouds with
+        a capacity that did not truncate.  Returns a dict with trace (S int64 [n, 23]: capi.MldFeatureTrace, see
+        FeatureTraces.records()) and, with list_capacity > 0, nb, seg, road and road_inl (S int32 [n, list_capacity]
+        each; a row holds the first min(count, list_capacity) entries of its list, the rest is not written).  No
+        synchronisation: torch's current stream is made to wait for the call; a host read synchronises as usual.
+        attach_traces() first."""
+        import torch
+        if self.feature_traces is None:
+            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.traces without attach_traces")
+        if clouds.get("cam") is None or clouds.get("pixel_map") is None:
+            raise ValueError("clouds: projected_clouds(cam=True, pixel_map=True) of this frame")
+        u_new, v_new = f["features"]
+        dev = next((t.device for t in u_new if t is not None), torch.device("cuda", self.est._device))
+        ns = [int(t.numel()) if t is not None else 0 for t in u_new]
+        cap = int(list_capacity)
+        names = ("nb", "seg", "road", "road_inl")
+        out = {"trace": [torch.empty((n, FeatureTraces.WORDS), dtype=torch.int64, device=dev) for n in ns]}
+        for name in names:
+            out[name] = [torch.empty((n, cap), dtype=torch.int32, device=dev) for n in ns] if cap else None
+        self.est._after_torch(*[t for t in u_new if t is not None][:1])
+        self.feature_traces.collect_tracks(u_new, v_new, clouds["pixel_map"], clouds["index"], clouds["cam"], out["trace"],
+                                           f["coeffs"] if planes else None, list(f["keep"][1]) if planes else None, cap,
+                                           *[out[name] for name in names])
+        self.est.orderTorchAfter()
+        return out
+
     def attach_labels(self) -> SemanticLabels:
         """The label assignment of the S sequences that labels() queues behind a step."""
         if self.semantic_labels is None:
@@ -987,4 +1136,7 @@ class TrackletBatch:
         if self.inliers is not None:
             self.inliers.close()
             self.inliers = None
+        if self.feature_traces is not None:
+            self.feature_traces.close()
+            self.feature_traces = None
         self.est.close()
