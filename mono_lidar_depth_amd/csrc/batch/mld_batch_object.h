@@ -1,10 +1,13 @@
-// mld_batch_object.h — what the batch objects on top of the public C-ABI have in common (mld_tracks, mld_labels,
+// mld_batch_object.h — the host side the batch objects on top of the public C-ABI have in common (mld_tracks, mld_labels,
 // mld_semantic_planes, mld_ransac_planes, mld_projected_clouds, mld_depth_reports, mld_plane_inliers, mld_feature_traces;
-// each a translation unit of its own that includes this header and include/mld.h only):
+// each a translation unit of its own that includes this header, include/mld.h and - for what their kernels share -
+// mld_batch_device.h only):
 //   Object         the fields every object has (context, stream, device, last error), fail() and the MLD_HIP check on them
 //   DescRing<D>    the per-call table of n_seq descriptors: staged on the host, copied into one of kGens pinned
 //                  generations and moved to device memory by a kernel on the object's stream
+//   CompactScratch the device scratch of a pass / scan / write stream compaction (mld_batch_device.h) and its sizes
 //   create_object / release_object / destroy_object   the skeleton of mld_*_create and mld_*_destroy
+//   no_object, misaligned, with_stride   the refusal of a call on no object, the alignment test, the 16 / 32 dispatch
 // The objects share these TYPES; every object has its own ring, and none of this is shared with the context's own
 // upload ring in mld_api.hip.
 #pragma once
@@ -16,6 +19,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../../include/mld.h"
@@ -44,6 +48,23 @@ struct Object {
 inline int fail(Object* o, int code, const char* text) {
     o->err = text;
     return code;
+}
+
+// A call on no object: "<fn>: null object (<arg>)" into the unit's text for mld_*_last_error(NULL).
+inline int no_object(char (&no_object_error)[512], const char* fn, const char* arg) {
+    std::snprintf(no_object_error, sizeof(no_object_error), "%s: null object (%s)", fn, arg);
+    return MLD_ERR_INVALID_ARG;
+}
+
+inline bool misaligned(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+// f(std::integral_constant<int, 16 or 32>) for the stride of a cloud record (anything else was refused before).
+template <typename F>
+void with_stride(int stride_bytes, F f) {
+    if (stride_bytes == 16)
+        f(std::integral_constant<int, 16>{});
+    else
+        f(std::integral_constant<int, 32>{});
 }
 
 #define MLD_HIP(o, expr)                                                                                   \
@@ -97,6 +118,29 @@ struct DescRing {
         if (up_base) (void)hipHostFree(up_base);
         for (int g = 0; g < kGens; g++)
             if (up_ev[g]) (void)hipEventDestroy(up_ev[g]);
+    }
+};
+
+// The device scratch of a stream compaction over sequences of up to max_items items: one 64-bit mask per group of 64
+// items, and per chunk of `chunk` items (+ 1: the total) `columns` counts side by side.
+struct CompactScratch {
+    unsigned long long* d_gm = nullptr;
+    int* d_cpre = nullptr;
+    long long groups_per_seq = 0;
+    long long chunks_per_seq = 0;
+
+    int allocate(Object* o, int n_seq, int64_t max_items, int chunk, int columns, bool masks = true) {
+        groups_per_seq = (long long)((max_items + 63) / 64);
+        chunks_per_seq = (long long)((max_items + chunk - 1) / chunk);
+        if (masks) MLD_HIP(o, hipMalloc((void**)&d_gm, (size_t)n_seq * (size_t)groups_per_seq * sizeof(unsigned long long)));
+        MLD_HIP(o, hipMalloc((void**)&d_cpre, (size_t)n_seq * (size_t)(chunks_per_seq + 1) * (size_t)columns * sizeof(int)));
+        return MLD_OK;
+    }
+
+    // After the stream has been synchronised (release_object).
+    void release() {
+        if (d_gm) (void)hipFree(d_gm);
+        if (d_cpre) (void)hipFree(d_cpre);
     }
 };
 

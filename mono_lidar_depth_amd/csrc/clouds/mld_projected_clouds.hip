@@ -17,9 +17,10 @@
 // Nothing of the size of the cloud is stored between the passes (the ballots are one bit per point).
 //
 // This translation unit uses the depth path through its public C-ABI only (mld_get_stream) and shares no internals with
-// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h).  The results are nevertheless bit for bit those
-// of the one-slot getters (tests/test_projected_clouds_gpu.py pins that): to_camera and to_image below are copies,
-// operation for operation, of that path's transform and projection, in f64 from the float coordinates, and this unit
+// it (descriptor ring, object skeleton and compaction scratch: ../batch/mld_batch_object.h; the compaction's device
+// pieces, load_xyz and to_camera: ../batch/mld_batch_device.h).  The results are nevertheless bit for bit those of the
+// one-slot getters (tests/test_projected_clouds_gpu.py pins that): the shared to_camera and to_image below restate,
+// operation for operation, that path's transform and projection, in f64 from the float coordinates, and this unit
 // is compiled without contraction like the rest of the library.
 #include <hip/hip_runtime.h>
 
@@ -27,15 +28,16 @@
 #include <cstdio>
 
 #include "../batch/mld_batch_object.h"
+#include "../batch/mld_batch_device.h"
 
 namespace {
 
-constexpr int kWave = 64;
+using namespace mld_batch;
+
 constexpr int kBlock = 256;
 constexpr int kGroupsPerWave = 4;                  // consecutive groups of 64 points a wavefront takes
 constexpr int kChunk = kBlock * kGroupsPerWave;    // 1024 points = 16 groups per block
 constexpr int kGroupsPerChunk = kChunk / kWave;
-constexpr int64_t kMaxPoints = 8388607;
 constexpr int kFillPerThread = 4;                  // cells a thread of k_pc_fill clears per step
 constexpr unsigned kFillMaxBlocks = 4096;          // per sequence; the blocks stride over larger maps
 
@@ -57,37 +59,6 @@ struct PcCalib {
     double f, cu, cv;
     int32_t W, H;
 };
-
-// The arrays of a descriptor are GPU memory: said to the compiler, their accesses are global_* instead of flat_*.
-#define PC_GLOBAL __attribute__((address_space(1)))
-template <typename T>
-__device__ __forceinline__ PC_GLOBAL T* as_global(T* p) {
-    return (PC_GLOBAL T*)p;
-}
-
-// A cloud record's first 16 bytes as ONE load, with the 4-byte alignment the C-ABI asks for (gfx950 takes multi-dword
-// global loads at any dword address).  Stride 32 reads the first half of its record the same way.
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef float4v float4u __attribute__((aligned(4)));
-
-template <int kStride>
-__device__ __forceinline__ void load_xyz(const unsigned char* __restrict__ cloud, int i, float& x, float& y, float& z) {
-    const float4v r = *(const PC_GLOBAL float4u*)(cloud + (size_t)i * (size_t)kStride);
-    x = r.x, y = r.y, z = r.z;
-}
-
-struct V3 {
-    double x, y, z;
-};
-
-// Raw float point -> camera frame (DepthEstimator.cpp:169,173)
-__device__ __forceinline__ V3 to_camera(const PcCalib& c, double x, double y, double z) {
-    V3 r;
-    r.x = c.T[3] + ((c.T[0] * x + c.T[1] * y) + c.T[2] * z);
-    r.y = c.T[7] + ((c.T[4] * x + c.T[5] * y) + c.T[6] * z);
-    r.z = c.T[11] + ((c.T[8] * x + c.T[9] * y) + c.T[10] * z);
-    return r;
-}
 
 // camera_pinhole.h:88-90: q = K p with all nine products, hnormalized.
 __device__ __forceinline__ void to_image(const PcCalib& c, V3 p, double& u, double& v) {
@@ -115,11 +86,11 @@ typedef int4v int4u __attribute__((aligned(4)));
 __global__ __launch_bounds__(kBlock) void k_pc_fill(const PcSeq* __restrict__ desc, long long cells) {
     int32_t* const map = desc[blockIdx.x].map;
     if (!map) return;  // (uniform in the block)
-    PC_GLOBAL int32_t* m = as_global(map);
+    MLD_BATCH_GLOBAL int32_t* m = as_global(map);
     const long long step = (long long)gridDim.y * kBlock * kFillPerThread;
     for (long long i = ((long long)blockIdx.y * kBlock + threadIdx.x) * kFillPerThread; i < cells; i += step) {
         if (i + kFillPerThread <= cells) {
-            *(PC_GLOBAL int4u*)(m + i) = int4v{-1, -1, -1, -1};
+            *(MLD_BATCH_GLOBAL int4u*)(m + i) = int4v{-1, -1, -1, -1};
         } else {
             for (long long j = i; j < cells; j++) m[j] = -1;
         }
@@ -139,7 +110,7 @@ __global__ __launch_bounds__(kBlock) void k_pc_pass(const PcSeq* __restrict__ de
     const int lane = (int)threadIdx.x & (kWave - 1), wave = (int)threadIdx.x >> 6;
     const int first = ((int)blockIdx.y * (kBlock / kWave) + wave) * kGroupsPerWave * kWave;  // the wavefront's first point
     unsigned long long* __restrict__ gm = gm_all + (size_t)blockIdx.x * (size_t)groups_per_seq;
-    PC_GLOBAL double* cam = as_global(q.cam);
+    MLD_BATCH_GLOBAL double* cam = as_global(q.cam);
     float x[kGroupsPerWave], y[kGroupsPerWave], z[kGroupsPerWave];
 #pragma unroll
     for (int k = 0; k < kGroupsPerWave; k++) {
@@ -151,7 +122,7 @@ __global__ __launch_bounds__(kBlock) void k_pc_pass(const PcSeq* __restrict__ de
 #pragma unroll
     for (int k = 0; k < kGroupsPerWave; k++) {
         const int i0 = first + k * kWave, i = i0 + lane;
-        const V3 pc = to_camera(c, (double)x[k], (double)y[k], (double)z[k]);
+        const V3 pc = to_camera(c.T, (double)x[k], (double)y[k], (double)z[k]);
         double u, v;
         to_image(c, pc, u, v);
         const bool f = (i < n) && is_visible(c, u, v);
@@ -165,48 +136,17 @@ __global__ __launch_bounds__(kBlock) void k_pc_pass(const PcSeq* __restrict__ de
         cnt += (int)__popcll(m);
     }
     if (lane == 0) wsum[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-#pragma unroll
-        for (int w = 0; w < kBlock / kWave; w++) t += wsum[w];
-        *as_global(cpre_all + (size_t)blockIdx.x * (size_t)(chunks_per_seq + 1) + blockIdx.y + 1) = t;
-    }
+    chunk_count(wsum, cpre_all, chunks_per_seq);
 }
 
 // Exclusive prefix over the chunk counts of a sequence, in place: cpre[c] = visible points ahead of chunk c; the total
 // goes to n_visible[s].  The loop carries the sum over any number of chunks (up to 8192).
 __global__ __launch_bounds__(256) void k_pc_scan(const PcSeq* __restrict__ desc, int* __restrict__ cpre_all,
                                                 long long chunks_per_seq, long long* __restrict__ n_visible) {
-    __shared__ int wsum[256 / kWave];
     const int n = desc[blockIdx.x].n;
     const int NC = (n + kChunk - 1) / kChunk;
-    int* __restrict__ cpre = cpre_all + (size_t)blockIdx.x * (size_t)(chunks_per_seq + 1);
-    const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), w = tid >> 6;
-    if (tid == 0) cpre[0] = 0;
-    int carry = 0;
-    for (int c0 = 0; c0 < NC; c0 += 256) {  // (uniform)
-        const int c = c0 + tid;
-        const int v = c < NC ? cpre[c + 1] : 0;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int t = __shfl_up(incl, d);
-            if (lane >= d) incl += t;
-        }
-        if (lane == kWave - 1) wsum[w] = incl;
-        __syncthreads();
-        int off = carry, total = 0;
-#pragma unroll
-        for (int k = 0; k < 256 / kWave; k++) {
-            off += k < w ? wsum[k] : 0;
-            total += wsum[k];
-        }
-        if (c < NC) cpre[c + 1] = off + incl;
-        carry += total;
-        __syncthreads();
-    }
-    if (tid == 0) n_visible[blockIdx.x] = (long long)carry;
+    const int total = scan_chunk_counts(cpre_all + (size_t)blockIdx.x * (size_t)(chunks_per_seq + 1), NC);
+    if (threadIdx.x == 0) n_visible[blockIdx.x] = (long long)total;
 }
 
 // Grid as the pass.  Every wavefront reads the (up to 16) masks of its block, one per lane, and scans their counts; the
@@ -227,37 +167,22 @@ __global__ __launch_bounds__(kBlock) void k_pc_write(const PcSeq* __restrict__ d
     const int G = (n + kWave - 1) / kWave;
     const int g_mine = b * kGroupsPerChunk + lane;  // lanes 0..15: the masks of the block
     const unsigned long long mine = (lane < kGroupsPerChunk && g_mine < G) ? gm[g_mine] : 0ull;
-    const int pop = (int)__popcll(mine);
-    int incl = pop;
-#pragma unroll
-    for (int d = 1; d < kGroupsPerChunk; d <<= 1) {
-        const int t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    const int ahead = incl - pop;  // visible points of the block ahead of this lane's group
-    const unsigned mine_lo = (unsigned)mine, mine_hi = (unsigned)(mine >> 32);
-    PC_GLOBAL double* uv = as_global(q.uv);
-    PC_GLOBAL int32_t* index = as_global(q.index);
-    PC_GLOBAL double* depth = as_global(q.depth);
+    MLD_BATCH_GLOBAL double* uv = as_global(q.uv);
+    MLD_BATCH_GLOBAL int32_t* index = as_global(q.index);
+    MLD_BATCH_GLOBAL double* depth = as_global(q.depth);
     // (the cross-lane reads while every lane is here)
     unsigned lo[kGroupsPerWave], hi[kGroupsPerWave];
     int first_rank[kGroupsPerWave];
-#pragma unroll
-    for (int k = 0; k < kGroupsPerWave; k++) {
-        const int gl = wave * kGroupsPerWave + k;  // the group within the block
-        lo[k] = (unsigned)__shfl((int)mine_lo, gl);
-        hi[k] = (unsigned)__shfl((int)mine_hi, gl);
-        first_rank[k] = base + __shfl(ahead, gl);
-    }
+    group_ranks<kGroupsPerChunk>(mine, base, lane, wave, lo, hi, first_rank);
 #pragma unroll
     for (int k = 0; k < kGroupsPerWave; k++) {
         const unsigned long long m = ((unsigned long long)hi[k] << 32) | lo[k];
         if (!((m >> lane) & 1ull)) continue;  // (a set bit is a point below n)
-        const int rank = first_rank[k] + (int)__builtin_amdgcn_mbcnt_hi(hi[k], __builtin_amdgcn_mbcnt_lo(lo[k], 0u));
+        const int rank = first_rank[k] + lane_rank(lo[k], hi[k]);
         const int i = ((b * kGroupsPerChunk + wave * kGroupsPerWave + k) << 6) + lane;
         float x, y, z;
         load_xyz<kStride>(q.cloud, i, x, y, z);
-        const V3 pc = to_camera(c, (double)x, (double)y, (double)z);
+        const V3 pc = to_camera(c.T, (double)x, (double)y, (double)z);
         double u, v;
         to_image(c, pc, u, v);
         if (rank < q.capacity) {
@@ -280,11 +205,8 @@ char g_error[512] = "";  // refusals without an object: mld_projected_clouds_las
 struct mld_projected_clouds : mld_batch::Object {
     int n_seq = 0;
     int64_t max_points = 0;
-    long long groups_per_seq = 0;  // 64-point groups of max_points
-    long long chunks_per_seq = 0;  // 1024-point chunks of max_points
     PcCalib calib{};
-    unsigned long long* d_gm = nullptr;  // visibility mask per group
-    int* d_cpre = nullptr;               // visible points ahead of every chunk (+ the total)
+    CompactScratch scratch;  // visibility mask per group; visible points ahead of every chunk (+ the total)
     mld_batch::DescRing<PcSeq> ring;
 };
 
@@ -293,19 +215,15 @@ namespace {
 int allocate(mld_projected_clouds* pc) {
     const int rc = pc->ring.allocate(pc, pc->n_seq);
     if (rc) return rc;
-    MLD_HIP(pc, hipMalloc((void**)&pc->d_gm, (size_t)pc->n_seq * (size_t)pc->groups_per_seq * sizeof(unsigned long long)));
-    MLD_HIP(pc, hipMalloc((void**)&pc->d_cpre, (size_t)pc->n_seq * (size_t)(pc->chunks_per_seq + 1) * sizeof(int)));
-    return MLD_OK;
+    return pc->scratch.allocate(pc, pc->n_seq, pc->max_points, kChunk, 1);
 }
 
-void free_own(mld_projected_clouds* pc) {
-    if (pc->d_gm) (void)hipFree(pc->d_gm);
-    if (pc->d_cpre) (void)hipFree(pc->d_cpre);
-}
+void free_own(mld_projected_clouds* pc) { pc->scratch.release(); }
 
 template <int kStride>
 void launch_all(mld_projected_clouds* pc, int chunks, bool any_map, int64_t* n_visible) {
     const unsigned S = (unsigned)pc->n_seq;
+    const CompactScratch& cs = pc->scratch;
     if (any_map) {
         const long long cells = (long long)pc->calib.W * pc->calib.H;
         const long long per_block = (long long)kBlock * kFillPerThread;
@@ -315,12 +233,12 @@ void launch_all(mld_projected_clouds* pc, int chunks, bool any_map, int64_t* n_v
     }
     if (chunks > 0)
         hipLaunchKernelGGL(k_pc_pass<kStride>, dim3(S, (unsigned)chunks), dim3(kBlock), 0, pc->stream, pc->ring.d_desc, pc->calib,
-                           pc->d_gm, pc->groups_per_seq, pc->d_cpre, pc->chunks_per_seq);
-    hipLaunchKernelGGL(k_pc_scan, dim3(S), dim3(256), 0, pc->stream, pc->ring.d_desc, pc->d_cpre, pc->chunks_per_seq,
+                           cs.d_gm, cs.groups_per_seq, cs.d_cpre, cs.chunks_per_seq);
+    hipLaunchKernelGGL(k_pc_scan, dim3(S), dim3(256), 0, pc->stream, pc->ring.d_desc, cs.d_cpre, cs.chunks_per_seq,
                        reinterpret_cast<long long*>(n_visible));
     if (chunks > 0)
         hipLaunchKernelGGL(k_pc_write<kStride>, dim3(S, (unsigned)chunks), dim3(kBlock), 0, pc->stream, pc->ring.d_desc, pc->calib,
-                           pc->d_gm, pc->groups_per_seq, pc->d_cpre, pc->chunks_per_seq);
+                           cs.d_gm, cs.groups_per_seq, cs.d_cpre, cs.chunks_per_seq);
 }
 
 }  // namespace
@@ -344,8 +262,6 @@ mld_projected_clouds* mld_projected_clouds_create(mld_ctx* ctx, int n_seq, int64
     auto init = [&](mld_projected_clouds* pc) {
         pc->n_seq = n_seq;
         pc->max_points = max_points;
-        pc->groups_per_seq = (long long)((max_points + kWave - 1) / kWave);
-        pc->chunks_per_seq = (long long)((max_points + kChunk - 1) / kChunk);
         for (int t = 0; t < 12; t++) pc->calib.T[t] = T_cam_lidar[t];
         pc->calib.f = camera->focal_length;
         pc->calib.cu = camera->principal_point_x;
@@ -366,10 +282,7 @@ int mld_projected_clouds_export_device(mld_projected_clouds* pc, const void* con
                                        const int64_t* capacity, int64_t* n_visible_out_dev, double* const* uv_out,
                                        int32_t* const* index_out, double* const* depth_out, double* const* cam_out,
                                        int32_t* const* map_out) {
-    if (!pc) {
-        std::snprintf(g_error, sizeof(g_error), "mld_projected_clouds_export_device: null object (pc)");
-        return MLD_ERR_INVALID_ARG;
-    }
+    if (!pc) return no_object(g_error, "mld_projected_clouds_export_device", "pc");
 #define PC_REFUSE(text) return fail(pc, MLD_ERR_INVALID_ARG, "mld_projected_clouds_export_device: " text)
     if (!pts_dev) PC_REFUSE("null table pts_dev");
     if (!n) PC_REFUSE("null table n");
@@ -387,7 +300,7 @@ int mld_projected_clouds_export_device(mld_projected_clouds* pc, const void* con
             return fail(pc, MLD_ERR_CAPACITY, "mld_projected_clouds_export_device: n exceeds the max_points of the object");
         if (n[s] > 0) {
             if (!pts_dev[s]) PC_REFUSE("null array pts_dev of a sequence with points");
-            if (reinterpret_cast<uintptr_t>(pts_dev[s]) & 3u) PC_REFUSE("pts_dev must be 4-byte aligned");
+            if (misaligned(pts_dev[s], 3u)) PC_REFUSE("pts_dev must be 4-byte aligned");
             if (capacity[s] > 0) {
                 if (!uv_out[s]) PC_REFUSE("null array uv_out of a sequence with points and capacity");
                 if (!index_out[s]) PC_REFUSE("null array index_out of a sequence with points and capacity");
@@ -414,10 +327,7 @@ int mld_projected_clouds_export_device(mld_projected_clouds* pc, const void* con
     const int rc = pc->ring.upload(pc);
     if (rc) return rc;
     const int chunks = (int)((longest + kChunk - 1) / kChunk);  // (<= 8192)
-    if (stride_bytes == 16)
-        launch_all<16>(pc, chunks, any_map, n_visible_out_dev);
-    else
-        launch_all<32>(pc, chunks, any_map, n_visible_out_dev);
+    with_stride(stride_bytes, [&](auto stride) { launch_all<decltype(stride)::value>(pc, chunks, any_map, n_visible_out_dev); });
     MLD_HIP(pc, hipGetLastError());
     return MLD_OK;
 }

@@ -257,10 +257,7 @@ const char* mld_labels_last_error(const mld_labels* lb) { return lb ? lb->err.c_
 int mld_labels_assign_device(mld_labels* lb, const uint8_t* const* label_image_dev, int rows, int cols, int row_stride_bytes,
                              int roi_width, int roi_height, const float* const* u, const float* const* v,
                              const int64_t* n_tracks, int16_t* const* label_out, int32_t* const* votes_out) {
-    if (!lb) {
-        std::snprintf(g_error, sizeof(g_error), "mld_labels_assign_device: null object (lb)");
-        return MLD_ERR_INVALID_ARG;
-    }
+    if (!lb) return mld_batch::no_object(g_error, "mld_labels_assign_device", "lb");
     if (rows < 1 || cols < 1) return fail(lb, MLD_ERR_INVALID_ARG, "mld_labels_assign_device: rows and cols must be >= 1");
     if ((int64_t)rows * cols > 0x7fffffff)
         return fail(lb, MLD_ERR_INVALID_ARG, "mld_labels_assign_device: rows * cols must be below 2^31");

@@ -21,10 +21,11 @@
 // pass, two counts in the write, and nothing of the cloud.
 //
 // This translation unit uses the depth path through its public C-ABI only (mld_get_stream) and shares no internals with
-// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h).  The results are nevertheless bit for bit those
-// of the one-slot getters (tests/test_plane_inliers_gpu.py pins that): to_camera below is a copy, operation for
-// operation, of that path's transform, in f64 from the float coordinates, and this unit is compiled without contraction
-// like the rest of the library.
+// it (descriptor ring, object skeleton and compaction scratch: ../batch/mld_batch_object.h; the compaction's device
+// pieces, load_xyz and to_camera: ../batch/mld_batch_device.h).  The results are nevertheless bit for bit those of the
+// one-slot getters (tests/test_plane_inliers_gpu.py pins that): the shared to_camera restates, operation for operation,
+// that path's transform, in f64 from the float coordinates, and this unit is compiled without contraction like the rest
+// of the library.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -32,17 +33,18 @@
 #include <cstdio>
 
 #include "../batch/mld_batch_object.h"
+#include "../batch/mld_batch_device.h"
 
 namespace {
 
-constexpr int kWave = 64;
+using namespace mld_batch;
+
 constexpr int kBlock = 256;
 constexpr int kGroupsPerWave = 4;                  // consecutive groups of 64 points a wavefront takes
 constexpr int kChunk = kBlock * kGroupsPerWave;    // 1024 points = 16 groups = 32 mask words per block
 constexpr int kGroupsPerChunk = kChunk / kWave;
 constexpr int kWordsPerWave = 2 * kGroupsPerWave;  // 32-bit mask words of a wavefront's groups
 constexpr int kWordsPerChunk = 2 * kGroupsPerChunk;
-constexpr int64_t kMaxPoints = 8388607;
 
 static_assert(sizeof(mld_plane_inlier_counts) == 16, "two int64 (include/mld.h)");
 
@@ -63,37 +65,6 @@ struct PiCalib {
     double thr;    // ransac_plane_treshold_camx
     int32_t use;   // ransac_plane_use_camx_treshold
 };
-
-// The arrays of a descriptor are GPU memory: said to the compiler, their accesses are global_* instead of flat_*.
-#define PI_GLOBAL __attribute__((address_space(1)))
-template <typename T>
-__device__ __forceinline__ PI_GLOBAL T* as_global(T* p) {
-    return (PI_GLOBAL T*)p;
-}
-
-// A cloud record's first 16 bytes as ONE load, with the 4-byte alignment the C-ABI asks for (gfx950 takes multi-dword
-// global loads at any dword address).  Stride 32 reads the first half of its record the same way.
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef float4v float4u __attribute__((aligned(4)));
-
-template <int kStride>
-__device__ __forceinline__ void load_xyz(const unsigned char* __restrict__ cloud, int i, float& x, float& y, float& z) {
-    const float4v r = *(const PI_GLOBAL float4u*)(cloud + (size_t)i * (size_t)kStride);
-    x = r.x, y = r.y, z = r.z;
-}
-
-struct V3 {
-    double x, y, z;
-};
-
-// Raw float point -> camera frame (DepthEstimator.cpp:169,173)
-__device__ __forceinline__ V3 to_camera(const PiCalib& c, double x, double y, double z) {
-    V3 r;
-    r.x = c.T[3] + ((c.T[0] * x + c.T[1] * y) + c.T[2] * z);
-    r.y = c.T[7] + ((c.T[4] * x + c.T[5] * y) + c.T[6] * z);
-    r.z = c.T[11] + ((c.T[8] * x + c.T[9] * y) + c.T[10] * z);
-    return r;
-}
 
 // Mask word w of a sequence of n points (w < ceil(n / 32)), the bits at and beyond n cleared: a caller's own mask may
 // carry anything there.
@@ -137,7 +108,7 @@ __global__ __launch_bounds__(kBlock) void k_pi_pass(const PiSeq* __restrict__ de
         if ((m >> lane) & 1ull) {  // (a set bit is a point below n)
             float x, y, z;
             load_xyz<kStride>(q.cloud, ((g0 + k) << 6) + lane, x, y, z);
-            const V3 pc = to_camera(c, (double)x, (double)y, (double)z);
+            const V3 pc = to_camera(c.T, (double)x, (double)y, (double)z);
             f = fabs(pc.x) <= c.thr;  // NaN fails (DepthEstimator.cpp:300-307)
         }
         const unsigned long long mc = __ballot(f);
@@ -171,13 +142,9 @@ __global__ __launch_bounds__(256) void k_pi_scan(const PiSeq* __restrict__ desc,
     int carry_in = 0, carry_cl = 0;
     for (int c0 = 0; c0 < NC; c0 += 256) {  // (uniform)
         const int c = c0 + tid;
-        int incl_in = c < NC ? cpre[2 * (c + 1)] : 0;
-        int incl_cl = (use && c < NC) ? cpre[2 * (c + 1) + 1] : 0;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int t = __shfl_up(incl_in, d), u = __shfl_up(incl_cl, d);
-            if (lane >= d) incl_in += t, incl_cl += u;
-        }
+        const IntPair incl =
+            scan_inclusive<kWave>(c < NC ? cpre[2 * (c + 1)] : 0, (use && c < NC) ? cpre[2 * (c + 1) + 1] : 0, lane);
+        const int incl_in = incl.a, incl_cl = incl.b;
         if (lane == kWave - 1) {
             wsum[0][w] = incl_in;
             wsum[1][w] = incl_cl;
@@ -225,13 +192,7 @@ __global__ __launch_bounds__(kBlock) void k_pi_write(const PiSeq* __restrict__ d
     const int w_mine = b * kWordsPerChunk + lane;  // lanes 0..31: the words of the block
     const unsigned word = (lane < kWordsPerChunk && w_mine < W) ? load_word(q.mask, w_mine, n) : 0u;
     const int pop = (int)__popc(word);
-    int incl = pop;
-#pragma unroll
-    for (int d = 1; d < kWordsPerChunk; d <<= 1) {
-        const int t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    const int ahead_in = incl - pop;  // inliers of the block ahead of this lane's word
+    const int ahead_in = scan_inclusive<kWordsPerChunk>(pop, lane) - pop;  // inliers of the block ahead of this lane's word
     // lanes 0..15: the filter's ballot of the block's groups that have an inlier
     const int pair = (lane & (kGroupsPerChunk - 1)) * 2;
     const unsigned own = (unsigned)__shfl((int)word, pair) | (unsigned)__shfl((int)word, pair + 1);
@@ -239,17 +200,11 @@ __global__ __launch_bounds__(kBlock) void k_pi_write(const PiSeq* __restrict__ d
     if (c.use && lane < kGroupsPerChunk && own != 0u)
         mine_cl = *as_global(gm_all + (size_t)blockIdx.x * (size_t)groups_per_seq + (size_t)(b * kGroupsPerChunk + lane));
     const int pop_cl = (int)__popcll(mine_cl);
-    int incl_cl = pop_cl;
-#pragma unroll
-    for (int d = 1; d < kGroupsPerChunk; d <<= 1) {
-        const int t = __shfl_up(incl_cl, d);
-        if (lane >= d) incl_cl += t;
-    }
-    const int ahead_cl = incl_cl - pop_cl;  // points of the cloud of the block ahead of this lane's group
+    const int ahead_cl = scan_inclusive<kGroupsPerChunk>(pop_cl, lane) - pop_cl;  // points of the cloud ahead of this lane's group
     const unsigned cl_lo = (unsigned)mine_cl, cl_hi = (unsigned)(mine_cl >> 32);
-    PI_GLOBAL int32_t* index = as_global(q.index);
-    PI_GLOBAL float* lidar = as_global(q.lidar);
-    PI_GLOBAL double* cam = as_global(q.cam);
+    MLD_BATCH_GLOBAL int32_t* index = as_global(q.index);
+    MLD_BATCH_GLOBAL float* lidar = as_global(q.lidar);
+    MLD_BATCH_GLOBAL double* cam = as_global(q.cam);
     // (the cross-lane reads while every lane is here)
     unsigned lo[kGroupsPerWave], hi[kGroupsPerWave], flo[kGroupsPerWave], fhi[kGroupsPerWave];
     int first_in[kGroupsPerWave], first_cl[kGroupsPerWave];
@@ -269,8 +224,8 @@ __global__ __launch_bounds__(kBlock) void k_pi_write(const PiSeq* __restrict__ d
         const unsigned long long m = ((unsigned long long)hi[k] << 32) | lo[k];
         if (!((m >> lane) & 1ull)) continue;  // (a set bit is a point below n)
         const unsigned long long mc = ((unsigned long long)fhi[k] << 32) | flo[k];
-        const int rank = first_in[k] + (int)__builtin_amdgcn_mbcnt_hi(hi[k], __builtin_amdgcn_mbcnt_lo(lo[k], 0u));
-        const int rank_cl = first_cl[k] + (int)__builtin_amdgcn_mbcnt_hi(fhi[k], __builtin_amdgcn_mbcnt_lo(flo[k], 0u));
+        const int rank = first_in[k] + lane_rank(lo[k], hi[k]);
+        const int rank_cl = first_cl[k] + lane_rank(flo[k], fhi[k]);
         const int i = ((b * kGroupsPerChunk + wave * kGroupsPerWave + k) << 6) + lane;
         const bool st_in = rank < q.capacity;
         const bool st_cam = cam && ((mc >> lane) & 1ull) && rank_cl < q.capacity;
@@ -284,7 +239,7 @@ __global__ __launch_bounds__(kBlock) void k_pi_write(const PiSeq* __restrict__ d
             lidar[3 * (size_t)rank + 2] = z;
         }
         if (st_cam) {
-            const V3 pc = to_camera(c, (double)x, (double)y, (double)z);
+            const V3 pc = to_camera(c.T, (double)x, (double)y, (double)z);
             cam[3 * (size_t)rank_cl] = pc.x;
             cam[3 * (size_t)rank_cl + 1] = pc.y;
             cam[3 * (size_t)rank_cl + 2] = pc.z;
@@ -299,11 +254,9 @@ char g_error[512] = "";  // refusals without an object: mld_plane_inliers_last_e
 struct mld_plane_inliers : mld_batch::Object {
     int n_seq = 0;
     int64_t max_points = 0;
-    long long groups_per_seq = 0;  // 64-point groups of max_points
-    long long chunks_per_seq = 0;  // 1024-point chunks of max_points
     PiCalib calib{};
-    unsigned long long* d_gm = nullptr;  // the filter's ballot per group (only with the filter on)
-    int* d_cpre = nullptr;               // inliers and cloud points ahead of every chunk (+ the totals)
+    CompactScratch scratch;  // the filter's ballot per group (only with the filter on); inliers and cloud points ahead of
+                             // every chunk (+ the totals)
     mld_batch::DescRing<PiSeq> ring;
 };
 
@@ -312,30 +265,23 @@ namespace {
 int allocate(mld_plane_inliers* pi) {
     const int rc = pi->ring.allocate(pi, pi->n_seq);
     if (rc) return rc;
-    if (pi->calib.use)
-        MLD_HIP(pi, hipMalloc((void**)&pi->d_gm, (size_t)pi->n_seq * (size_t)pi->groups_per_seq * sizeof(unsigned long long)));
-    MLD_HIP(pi, hipMalloc((void**)&pi->d_cpre, (size_t)pi->n_seq * (size_t)(pi->chunks_per_seq + 1) * 2 * sizeof(int)));
-    return MLD_OK;
+    return pi->scratch.allocate(pi, pi->n_seq, pi->max_points, kChunk, 2, pi->calib.use != 0);
 }
 
-void free_own(mld_plane_inliers* pi) {
-    if (pi->d_gm) (void)hipFree(pi->d_gm);
-    if (pi->d_cpre) (void)hipFree(pi->d_cpre);
-}
-
-bool misaligned(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+void free_own(mld_plane_inliers* pi) { pi->scratch.release(); }
 
 template <int kStride>
 void launch_all(mld_plane_inliers* pi, int chunks, bool any_list, mld_plane_inlier_counts* counts) {
     const unsigned S = (unsigned)pi->n_seq;
+    const CompactScratch& cs = pi->scratch;
     if (chunks > 0)
         hipLaunchKernelGGL(k_pi_pass<kStride>, dim3(S, (unsigned)chunks), dim3(kBlock), 0, pi->stream, pi->ring.d_desc, pi->calib,
-                           pi->d_gm, pi->groups_per_seq, pi->d_cpre, pi->chunks_per_seq);
-    hipLaunchKernelGGL(k_pi_scan, dim3(S), dim3(256), 0, pi->stream, pi->ring.d_desc, (int)pi->calib.use, pi->d_cpre,
-                       pi->chunks_per_seq, reinterpret_cast<long long*>(counts));
+                           cs.d_gm, cs.groups_per_seq, cs.d_cpre, cs.chunks_per_seq);
+    hipLaunchKernelGGL(k_pi_scan, dim3(S), dim3(256), 0, pi->stream, pi->ring.d_desc, (int)pi->calib.use, cs.d_cpre,
+                       cs.chunks_per_seq, reinterpret_cast<long long*>(counts));
     if (chunks > 0 && any_list)
         hipLaunchKernelGGL(k_pi_write<kStride>, dim3(S, (unsigned)chunks), dim3(kBlock), 0, pi->stream, pi->ring.d_desc, pi->calib,
-                           pi->d_gm, pi->groups_per_seq, pi->d_cpre, pi->chunks_per_seq);
+                           cs.d_gm, cs.groups_per_seq, cs.d_cpre, cs.chunks_per_seq);
 }
 
 }  // namespace
@@ -356,8 +302,6 @@ mld_plane_inliers* mld_plane_inliers_create(mld_ctx* ctx, int n_seq, int64_t max
     auto init = [&](mld_plane_inliers* pi) {
         pi->n_seq = n_seq;
         pi->max_points = max_points;
-        pi->groups_per_seq = (long long)((max_points + kWave - 1) / kWave);
-        pi->chunks_per_seq = (long long)((max_points + kChunk - 1) / kChunk);
         for (int t = 0; t < 12; t++) pi->calib.T[t] = T_cam_lidar[t];
         pi->calib.thr = params->ransac_plane_treshold_camx;
         pi->calib.use = params->ransac_plane_use_camx_treshold ? 1 : 0;
@@ -374,10 +318,7 @@ int mld_plane_inliers_export_device(mld_plane_inliers* pi, const void* const* pt
                                     const uint32_t* const* mask_dev, const int64_t* capacity,
                                     mld_plane_inlier_counts* counts_out_dev, int32_t* const* index_out,
                                     float* const* lidar_out, double* const* cam_out) {
-    if (!pi) {
-        std::snprintf(g_error, sizeof(g_error), "mld_plane_inliers_export_device: null object (pi)");
-        return MLD_ERR_INVALID_ARG;
-    }
+    if (!pi) return no_object(g_error, "mld_plane_inliers_export_device", "pi");
 #define PI_REFUSE(text) return fail(pi, MLD_ERR_INVALID_ARG, "mld_plane_inliers_export_device: " text)
     if (!pts_dev) PI_REFUSE("null table pts_dev");
     if (!n) PI_REFUSE("null table n");
@@ -426,10 +367,7 @@ int mld_plane_inliers_export_device(mld_plane_inliers* pi, const void* const* pt
     const int rc = pi->ring.upload(pi);
     if (rc) return rc;
     const int chunks = (int)((longest + kChunk - 1) / kChunk);  // (<= 8192)
-    if (stride_bytes == 16)
-        launch_all<16>(pi, chunks, any_list, counts_out_dev);
-    else
-        launch_all<32>(pi, chunks, any_list, counts_out_dev);
+    with_stride(stride_bytes, [&](auto stride) { launch_all<decltype(stride)::value>(pi, chunks, any_list, counts_out_dev); });
     MLD_HIP(pi, hipGetLastError());
     return MLD_OK;
 }

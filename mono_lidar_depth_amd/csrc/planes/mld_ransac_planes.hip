@@ -22,9 +22,10 @@
 // refinement are assembled over the sample once every thread has taken what it needs from it.
 //
 // This translation unit uses the depth path through its public C-ABI only (mld_get_stream) and shares no internals with
-// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h).  The results are nevertheless bit for bit those
-// of mld_estimate_ground_plane (tests/test_ransac_planes_gpu.py pins that): the helpers below - mix, sample_pos,
-// plane_from, the distance, the stopping rule, the Jacobi - are copies of that path's arithmetic, and the float sums of
+// it (descriptor ring, object skeleton and compaction scratch: ../batch/mld_batch_object.h; the compaction's device
+// pieces, load_xyz and the Jacobi: ../batch/mld_batch_device.h).  The results are nevertheless bit for bit those
+// of mld_estimate_ground_plane (tests/test_ransac_planes_gpu.py pins that): the helpers - mix, sample_pos,
+// plane_from, the distance, the stopping rule, the Jacobi - restate that path's arithmetic, and the float sums of
 // the refinement keep its association: inlier q of the ordered list into partial q % 256, the partials in index order.
 #include <hip/hip_runtime.h>
 
@@ -33,13 +34,14 @@
 #include <cstdio>
 
 #include "../batch/mld_batch_object.h"
+#include "../batch/mld_batch_device.h"
 
 namespace {
 
-constexpr int kWave = 64;
+using namespace mld_batch;
+
 constexpr int kSample = 6000;   // RansacPlane.cpp:32
 constexpr int kPartials = 256;
-constexpr int64_t kMaxPoints = 8388607;
 
 // the streaming kernel of the pass-through
 constexpr int kPassBlock = 256;
@@ -85,24 +87,6 @@ struct RpParams {
     int32_t n_draws, max_it, use_refinement, pass;
     float lo, hi;
 };
-
-// The arrays of a descriptor are GPU memory: said to the compiler, their accesses are global_* instead of flat_*.
-#define RP_GLOBAL __attribute__((address_space(1)))
-template <typename T>
-__device__ __forceinline__ RP_GLOBAL T* as_global(T* p) {
-    return (RP_GLOBAL T*)p;
-}
-
-// A cloud record's first 16 bytes as ONE load, with the 4-byte alignment the C-ABI asks for (gfx950 takes multi-dword
-// global loads at any dword address).  Stride 32 reads the first half of its record the same way.
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef float4v float4u __attribute__((aligned(4)));
-
-template <int kStride>
-__device__ __forceinline__ void load_xyz(const unsigned char* __restrict__ cloud, uint32_t i, float& x, float& y, float& z) {
-    const float4v r = *(const RP_GLOBAL float4u*)(cloud + (size_t)i * (size_t)kStride);
-    x = r.x, y = r.y, z = r.z;
-}
 
 __host__ __device__ inline uint32_t mix(uint32_t a, uint32_t b, uint32_t c) {
     uint32_t h = a * 0x9E3779B1u;
@@ -212,51 +196,6 @@ __device__ inline void count_inliers(const float* sx, const float* sy, const flo
     }
 }
 
-// Symmetric 3x3 Jacobi (double), smallest eigenvector; s = xx,xy,xz,yy,yz,zz
-__device__ inline void smallest_eigvec(const double s[6], double n0[3]) {
-    double a[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}};
-    double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 64; sweep++) {
-        double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
-        double diag = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2];
-        if (!(off > 1e-300) || off <= 1e-32 * diag) break;
-        for (int p = 0; p < 2; p++)
-            for (int q = p + 1; q < 3; q++) {
-                double apq = a[p][q];
-                if (apq == 0.0) continue;
-                double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-                double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-                for (int k = 0; k < 3; k++) {
-                    double akp = a[k][p], akq = a[k][q];
-                    a[k][p] = cs * akp - sn * akq;
-                    a[k][q] = sn * akp + cs * akq;
-                }
-                for (int k = 0; k < 3; k++) {
-                    double apk = a[p][k], aqk = a[q][k];
-                    a[p][k] = cs * apk - sn * aqk;
-                    a[q][k] = sn * apk + cs * aqk;
-                }
-                for (int k = 0; k < 3; k++) {
-                    double vkp = v[k][p], vkq = v[k][q];
-                    v[k][p] = cs * vkp - sn * vkq;
-                    v[k][q] = sn * vkp + cs * vkq;
-                }
-            }
-    }
-    // index of the smallest diagonal entry, ties resolved like a stable ascending sort of (d0,d1,d2)
-    int i0 = 0;
-    double d0 = a[0][0];
-    if (a[1][1] < d0) {
-        d0 = a[1][1];
-        i0 = 1;
-    }
-    if (a[2][2] < d0) i0 = 2;
-    n0[0] = v[0][i0];
-    n0[1] = v[1][i0];
-    n0[2] = v[2][i0];
-}
-
 // pcl::PassThrough on z with float limits (:57-64): candidate = finite && lo <= z <= hi.  Grid (sequence, chunk of 1024
 // points).  gm: one 64-bit mask per 64 points, cpre[c + 1]: the candidates of chunk c (k_rp_scan makes them a prefix).
 template <int kStride>
@@ -287,46 +226,15 @@ __global__ __launch_bounds__(kPassBlock) void k_rp_pass(const RpSeq* __restrict_
         cnt += (int)__popcll(m);
     }
     if (lane == 0) wsum[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-#pragma unroll
-        for (int w = 0; w < kPassBlock / kWave; w++) t += wsum[w];
-        *as_global(cpre_all + (size_t)blockIdx.x * (size_t)(chunks_per_seq + 1) + blockIdx.y + 1) = t;
-    }
+    chunk_count(wsum, cpre_all, chunks_per_seq);
 }
 
 // Exclusive prefix over the chunk counts of a sequence, in place: cpre[c] = candidates ahead of chunk c, cpre[NC] = all.
 __global__ __launch_bounds__(256) void k_rp_scan(const RpSeq* __restrict__ desc, int* __restrict__ cpre_all,
                                                 long long chunks_per_seq) {
-    __shared__ int wsum[256 / kWave];
     const int n = desc[blockIdx.x].n;
     const int NC = (n + kChunk - 1) / kChunk;
-    int* __restrict__ cpre = cpre_all + (size_t)blockIdx.x * (size_t)(chunks_per_seq + 1);
-    const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), w = tid >> 6;
-    if (tid == 0) cpre[0] = 0;
-    int carry = 0;
-    for (int c0 = 0; c0 < NC; c0 += 256) {  // (uniform)
-        const int c = c0 + tid;
-        const int v = c < NC ? cpre[c + 1] : 0;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int t = __shfl_up(incl, d);
-            if (lane >= d) incl += t;
-        }
-        if (lane == kWave - 1) wsum[w] = incl;
-        __syncthreads();
-        int off = carry, total = 0;
-#pragma unroll
-        for (int k = 0; k < 256 / kWave; k++) {
-            off += k < w ? wsum[k] : 0;
-            total += wsum[k];
-        }
-        if (c < NC) cpre[c + 1] = off + incl;
-        carry += total;
-        __syncthreads();
-    }
+    (void)scan_chunk_counts(cpre_all + (size_t)blockIdx.x * (size_t)(chunks_per_seq + 1), NC);
 }
 
 // One block per sequence: the whole estimator.  Four wavefronts per SIMD (at most 128 registers): two blocks per CU.
@@ -353,7 +261,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     const RpSeq q = desc[s];
     const int n = q.n;
     const uint32_t seed = q.seed;
-    RP_GLOBAL uint32_t* gmask = as_global(q.mask);
+    MLD_BATCH_GLOBAL uint32_t* gmask = as_global(q.mask);
     mld_ransac_plane_result* r = res + s;
 
     // the mask words are cleared before anything else: every way out below leaves a mask of zeros behind
@@ -596,7 +504,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     if (w == 0) {  // exclusive prefix of the words' counts, two words per lane
         const int v0 = lane < n_words ? (int)__popcll(inl[lane]) : 0;
         const int v1 = kWave + lane < n_words ? (int)__popcll(inl[kWave + lane]) : 0;
-        int i0 = v0, i1 = v1;
+        int i0 = v0, i1 = v1;  // (not scan_inclusive: it costs this kernel three instructions, profiles/batch_device_header.md)
 #pragma unroll
         for (int d = 1; d < kWave; d <<= 1) {
             const int t0 = __shfl_up(i0, d), t1 = __shfl_up(i1, d);
@@ -695,11 +603,8 @@ char g_error[512] = "";  // refusals without an object: mld_ransac_planes_last_e
 struct mld_ransac_planes : mld_batch::Object {
     int n_seq = 0;
     int64_t max_points = 0;
-    long long groups_per_seq = 0;  // 64-point groups of max_points
-    long long chunks_per_seq = 0;  // 1024-point chunks of max_points
     RpParams P{};
-    unsigned long long* d_gm = nullptr;  // pass-through: candidate mask per group
-    int* d_cpre = nullptr;               // pass-through: candidates ahead of every chunk (+ the total)
+    CompactScratch scratch;  // pass-through: candidate mask per group; candidates ahead of every chunk (+ the total)
     mld_batch::DescRing<RpSeq> ring;
 };
 
@@ -708,8 +613,8 @@ namespace {
 int allocate(mld_ransac_planes* rp) {
     const int rc = rp->ring.allocate(rp, rp->n_seq);
     if (rc) return rc;
-    MLD_HIP(rp, hipMalloc((void**)&rp->d_gm, (size_t)rp->n_seq * (size_t)rp->groups_per_seq * sizeof(unsigned long long)));
-    MLD_HIP(rp, hipMalloc((void**)&rp->d_cpre, (size_t)rp->n_seq * (size_t)(rp->chunks_per_seq + 1) * sizeof(int)));
+    const int rs = rp->scratch.allocate(rp, rp->n_seq, rp->max_points, kChunk, 1);
+    if (rs) return rs;
     // (the limit on dynamic LDS is an attribute of the function on a device)
     MLD_HIP(rp, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rp_estimate<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     kLdsBytes));
@@ -718,22 +623,20 @@ int allocate(mld_ransac_planes* rp) {
     return MLD_OK;
 }
 
-void free_own(mld_ransac_planes* rp) {
-    if (rp->d_gm) (void)hipFree(rp->d_gm);
-    if (rp->d_cpre) (void)hipFree(rp->d_cpre);
-}
+void free_own(mld_ransac_planes* rp) { rp->scratch.release(); }
 
 template <int kStride>
 void launch_all(mld_ransac_planes* rp, int chunks, mld_ransac_plane_result* res) {
     const unsigned S = (unsigned)rp->n_seq;
+    const CompactScratch& cs = rp->scratch;
     if (rp->P.pass) {
         if (chunks > 0)
             hipLaunchKernelGGL(k_rp_pass<kStride>, dim3(S, (unsigned)chunks), dim3(kPassBlock), 0, rp->stream, rp->ring.d_desc,
-                               rp->P.lo, rp->P.hi, rp->d_gm, rp->groups_per_seq, rp->d_cpre, rp->chunks_per_seq);
-        hipLaunchKernelGGL(k_rp_scan, dim3(S), dim3(256), 0, rp->stream, rp->ring.d_desc, rp->d_cpre, rp->chunks_per_seq);
+                               rp->P.lo, rp->P.hi, cs.d_gm, cs.groups_per_seq, cs.d_cpre, cs.chunks_per_seq);
+        hipLaunchKernelGGL(k_rp_scan, dim3(S), dim3(256), 0, rp->stream, rp->ring.d_desc, cs.d_cpre, cs.chunks_per_seq);
     }
-    hipLaunchKernelGGL(k_rp_estimate<kStride>, dim3(S), dim3(kThreads), kLdsBytes, rp->stream, rp->ring.d_desc, rp->P, rp->d_gm,
-                       rp->groups_per_seq, rp->d_cpre, rp->chunks_per_seq, res);
+    hipLaunchKernelGGL(k_rp_estimate<kStride>, dim3(S), dim3(kThreads), kLdsBytes, rp->stream, rp->ring.d_desc, rp->P, cs.d_gm,
+                       cs.groups_per_seq, cs.d_cpre, cs.chunks_per_seq, res);
 }
 
 }  // namespace
@@ -755,8 +658,6 @@ mld_ransac_planes* mld_ransac_planes_create(mld_ctx* ctx, int n_seq, int64_t max
     auto init = [&](mld_ransac_planes* rp) {
         rp->n_seq = n_seq;
         rp->max_points = max_points;
-        rp->groups_per_seq = (long long)((max_points + kWave - 1) / kWave);
-        rp->chunks_per_seq = (long long)((max_points + kChunk - 1) / kChunk);
         RpParams& P = rp->P;
         P.probability = params->ransac_plane_probability;
         P.thr = params->ransac_plane_distance_treshold;
@@ -780,10 +681,7 @@ const char* mld_ransac_planes_last_error(const mld_ransac_planes* rp) { return r
 int mld_ransac_planes_estimate_device(mld_ransac_planes* rp, const void* const* pts_dev, const int64_t* n, int stride_bytes,
                                       const uint32_t* seeds, mld_ransac_plane_result* result_out_dev,
                                       uint32_t* const* mask_out_dev) {
-    if (!rp) {
-        std::snprintf(g_error, sizeof(g_error), "mld_ransac_planes_estimate_device: null object (rp)");
-        return MLD_ERR_INVALID_ARG;
-    }
+    if (!rp) return no_object(g_error, "mld_ransac_planes_estimate_device", "rp");
 #define RP_REFUSE(text) return fail(rp, MLD_ERR_INVALID_ARG, "mld_ransac_planes_estimate_device: " text)
     if (!pts_dev) RP_REFUSE("null table pts_dev");
     if (!n) RP_REFUSE("null table n");
@@ -800,7 +698,7 @@ int mld_ransac_planes_estimate_device(mld_ransac_planes* rp, const void* const* 
         if (n[s] > 0) {
             if (!pts_dev[s]) RP_REFUSE("null array pts_dev of a sequence with points");
             if (!mask_out_dev[s]) RP_REFUSE("null array mask_out_dev of a sequence with points");
-            if ((reinterpret_cast<uintptr_t>(pts_dev[s]) | reinterpret_cast<uintptr_t>(mask_out_dev[s])) & 3u)
+            if (misaligned(pts_dev[s], 3u) || misaligned(mask_out_dev[s], 3u))
                 RP_REFUSE("pts_dev and mask_out_dev must be 4-byte aligned");
         }
         if (n[s] > longest) longest = n[s];
@@ -817,10 +715,7 @@ int mld_ransac_planes_estimate_device(mld_ransac_planes* rp, const void* const* 
     const int rc = rp->ring.upload(rp);
     if (rc) return rc;
     const int chunks = (int)((longest + kChunk - 1) / kChunk);  // (<= 8192)
-    if (stride_bytes == 16)
-        launch_all<16>(rp, chunks, result_out_dev);
-    else
-        launch_all<32>(rp, chunks, result_out_dev);
+    with_stride(stride_bytes, [&](auto stride) { launch_all<decltype(stride)::value>(rp, chunks, result_out_dev); });
     MLD_HIP(rp, hipGetLastError());
     return MLD_OK;
 }

@@ -13,9 +13,10 @@
 //   k_sp_fit<1>      one block per sequence: refit, the record
 //
 // This translation unit uses the depth path through its public C-ABI only (mld_get_stream) and shares no internals with
-// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h).  The results are nevertheless bit for bit those
-// of mld_estimate_semantic_plane_device (tests/test_semantic_planes_gpu.py pins that): the helpers below - plane
-// distance, smallest eigenvector of the 3x3 covariance, group reduction - are copies of that path's arithmetic, and the float moment sums keep its association:
+// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h; load_xyz and the smallest eigenvector of the 3x3
+// covariance, shared with mld_ransac_planes: ../batch/mld_batch_device.h).  The results are nevertheless bit for bit those
+// of mld_estimate_semantic_plane_device (tests/test_semantic_planes_gpu.py pins that): the helpers - plane distance,
+// eigenvector, group reduction - restate that path's arithmetic, and the float moment sums keep its association:
 //   the nine terms of a member (+0.0f for a non-member) over a GROUP of 64 consecutive points by the xor tree 32, 16, ..., 1;
 //   the group sums, in group order, into 256 interleaved partials (group g -> partial g % 256);
 //   the partials combined in index order.
@@ -27,15 +28,16 @@
 #include <cstdio>
 
 #include "../batch/mld_batch_object.h"
+#include "../batch/mld_batch_device.h"
 
 namespace {
 
-constexpr int kWave = 64;
+using namespace mld_batch;
+
 constexpr int kBlock = 256;
 constexpr int kPartials = 256;
 constexpr int kGroupsPerWave = 4;    // consecutive groups a wavefront of the streaming kernels takes (loads issued up front)
 constexpr int kBlockPoints = kBlock * kGroupsPerWave;  // 1024 points = 16 groups per block
-constexpr int64_t kMaxPoints = 8388607;
 
 // One sequence of one call.  Host-made, staged through the descriptor ring (mld_batch::DescRing).
 struct SpSeq {
@@ -63,24 +65,6 @@ struct GroupSums {
 };
 static_assert(sizeof(GroupSums) == 40, "40 bytes of scratch per 64 points");
 static_assert(sizeof(mld_semantic_plane_result) == 32, "mld.h");
-
-// The arrays of a descriptor are GPU memory: said to the compiler, their accesses are global_* instead of flat_*.
-#define SP_GLOBAL __attribute__((address_space(1)))
-template <typename T>
-__device__ __forceinline__ SP_GLOBAL T* as_global(T* p) {
-    return (SP_GLOBAL T*)p;
-}
-
-// A cloud record's first 16 bytes as ONE load, with the 4-byte alignment the C-ABI asks for (gfx950 takes multi-dword
-// global loads at any dword address).  Stride 32 reads the first half of its record the same way.
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef float4v float4u __attribute__((aligned(4)));
-
-template <int kStride>
-__device__ __forceinline__ void load_xyz(const unsigned char* __restrict__ cloud, int i, float& x, float& y, float& z) {
-    const float4v r = *(const SP_GLOBAL float4u*)(cloud + (size_t)i * (size_t)kStride);
-    x = r.x, y = r.y, z = r.z;
-}
 
 __device__ __forceinline__ float plane_dist(const float c[4], float x, float y, float z) {
     return fabsf(c[0] * x + c[1] * y + c[2] * z + c[3]);
@@ -124,7 +108,7 @@ __device__ __forceinline__ void group_reduce(bool member, float x, float y, floa
     tree_step<1>(a);
     const int cnt = (int)__popcll(__ballot(member));
     if (lane == 0) {
-        SP_GLOBAL float* o = as_global(out->s);
+        MLD_BATCH_GLOBAL float* o = as_global(out->s);
 #pragma unroll
         for (int t = 0; t < 9; t++) o[t] = a[t];
         *as_global(&out->count) = cnt;
@@ -216,51 +200,6 @@ __global__ __launch_bounds__(kBlock) void k_sp_select(const SpSeq* __restrict__ 
         if ((lane & 31) == 0 && w < words) as_global(q.mask)[w] = (uint32_t)(lane ? (m >> 32) : m);
         if (live) group_reduce(flag, x[k], y[k], z[k], gs + (i0 >> 6), lane);
     }
-}
-
-// Symmetric 3x3 Jacobi (double), smallest eigenvector; s = xx,xy,xz,yy,yz,zz
-__device__ inline void smallest_eigvec(const double s[6], double n0[3]) {
-    double a[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}};
-    double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 64; sweep++) {
-        double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
-        double diag = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2];
-        if (!(off > 1e-300) || off <= 1e-32 * diag) break;
-        for (int p = 0; p < 2; p++)
-            for (int q = p + 1; q < 3; q++) {
-                double apq = a[p][q];
-                if (apq == 0.0) continue;
-                double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-                double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-                for (int k = 0; k < 3; k++) {
-                    double akp = a[k][p], akq = a[k][q];
-                    a[k][p] = cs * akp - sn * akq;
-                    a[k][q] = sn * akp + cs * akq;
-                }
-                for (int k = 0; k < 3; k++) {
-                    double apk = a[p][k], aqk = a[q][k];
-                    a[p][k] = cs * apk - sn * aqk;
-                    a[q][k] = sn * apk + cs * aqk;
-                }
-                for (int k = 0; k < 3; k++) {
-                    double vkp = v[k][p], vkq = v[k][q];
-                    v[k][p] = cs * vkp - sn * vkq;
-                    v[k][q] = sn * vkp + cs * vkq;
-                }
-            }
-    }
-    // index of the smallest diagonal entry, ties resolved like a stable ascending sort of (d0,d1,d2)
-    int i0 = 0;
-    double d0 = a[0][0];
-    if (a[1][1] < d0) {
-        d0 = a[1][1];
-        i0 = 1;
-    }
-    if (a[2][2] < d0) i0 = 2;
-    n0[0] = v[0][i0];
-    n0[1] = v[1][i0];
-    n0[2] = v[2][i0];
 }
 
 // optimizeModelCoefficients from the group sums of one sequence: fewer than 4 members return the fallback.  One block of
@@ -422,10 +361,7 @@ int mld_semantic_planes_estimate_device(mld_semantic_planes* sp, const void* con
                                         const uint8_t* const* label_image_dev, int rows, int cols, int row_stride_bytes,
                                         const int32_t* ground_labels, int n_labels, double inlier_threshold,
                                         mld_semantic_plane_result* result_out_dev, uint32_t* const* mask_out_dev) {
-    if (!sp) {
-        std::snprintf(g_error, sizeof(g_error), "mld_semantic_planes_estimate_device: null object (sp)");
-        return MLD_ERR_INVALID_ARG;
-    }
+    if (!sp) return no_object(g_error, "mld_semantic_planes_estimate_device", "sp");
 #define SP_REFUSE(text) return fail(sp, MLD_ERR_INVALID_ARG, "mld_semantic_planes_estimate_device: " text)
     if (!pts_dev) SP_REFUSE("null table pts_dev");
     if (!n) SP_REFUSE("null table n");
@@ -447,7 +383,7 @@ int mld_semantic_planes_estimate_device(mld_semantic_planes* sp, const void* con
             if (!pts_dev[s]) SP_REFUSE("null array pts_dev of a sequence with points");
             if (!label_image_dev[s]) SP_REFUSE("null array label_image_dev of a sequence with points");
             if (!mask_out_dev[s]) SP_REFUSE("null array mask_out_dev of a sequence with points");
-            if ((reinterpret_cast<uintptr_t>(pts_dev[s]) | reinterpret_cast<uintptr_t>(mask_out_dev[s])) & 3u)
+            if (misaligned(pts_dev[s], 3u) || misaligned(mask_out_dev[s], 3u))
                 SP_REFUSE("pts_dev and mask_out_dev must be 4-byte aligned");
         }
         if (n[s] > longest) longest = n[s];
@@ -469,10 +405,8 @@ int mld_semantic_planes_estimate_device(mld_semantic_planes* sp, const void* con
     if (rc) return rc;
     const SpGeom g{rows, cols, row_stride_bytes};
     const int chunks = (int)((longest + kBlockPoints - 1) / kBlockPoints);  // (<= 8192)
-    if (stride_bytes == 16)
-        launch_all<16>(sp, chunks, g, ls, inlier_threshold, result_out_dev);
-    else
-        launch_all<32>(sp, chunks, g, ls, inlier_threshold, result_out_dev);
+    with_stride(stride_bytes,
+                [&](auto stride) { launch_all<decltype(stride)::value>(sp, chunks, g, ls, inlier_threshold, result_out_dev); });
     MLD_HIP(sp, hipGetLastError());
     return MLD_OK;
 }

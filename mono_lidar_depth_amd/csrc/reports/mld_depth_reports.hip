@@ -19,7 +19,8 @@
 // the integer pixel that layer evaluates.
 //
 // This translation unit uses the depth path through its public C-ABI only (mld_get_stream) and shares no internals with
-// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h).  The point is the arithmetic of the host shim's
+// it (descriptor ring, object skeleton and compaction scratch: ../batch/mld_batch_object.h; the compaction's device
+// pieces: ../batch/mld_batch_device.h).  The point is the arithmetic of the host shim's
 // getCloudInterpolated, operation for operation in f64, and this unit is compiled without contraction like the rest of
 // the library.
 #include <hip/hip_runtime.h>
@@ -29,17 +30,18 @@
 #include <cstdio>
 
 #include "../batch/mld_batch_object.h"
+#include "../batch/mld_batch_device.h"
 
 namespace {
 
-constexpr int kWave = 64;
+using namespace mld_batch;
+
 constexpr int kBlock = 256;
 constexpr int kGroupsPerWave = 4;                // consecutive groups of 64 features a wavefront takes
 constexpr int kChunk = kBlock * kGroupsPerWave;  // 1024 features = 16 groups per block
 constexpr int kGroupsPerChunk = kChunk / kWave;
 constexpr int kBins = MLD_RESULT_TYPE_COUNT + 1;  // 21 types + other
 constexpr int kScanRows = 256 / kBins;            // rows of kBins threads that sum the chunk histograms (11)
-constexpr int64_t kMaxFeatures = 16777216;
 
 static_assert(sizeof(mld_depth_report) == 192 && sizeof(mld_depth_report) == 8 * (kBins + 2), "24 int64 (include/mld.h)");
 
@@ -60,13 +62,6 @@ struct DrCam {
     double f, cu, cv;
 };
 
-// The arrays of a descriptor are GPU memory: said to the compiler, their accesses are global_* instead of flat_*.
-#define DR_GLOBAL __attribute__((address_space(1)))
-template <typename T>
-__device__ __forceinline__ DR_GLOBAL T* as_global(T* p) {
-    return (DR_GLOBAL T*)p;
-}
-
 // (u, v) of a feature as ONE load, with the 8-byte alignment the C-ABI asks for (gfx950 takes multi-dword global loads at
 // any dword address).
 typedef double double2v __attribute__((ext_vector_type(2)));
@@ -79,7 +74,7 @@ struct LoadF64 {
         return as_global(static_cast<const double*>(q.depth))[i];
     }
     static __device__ __forceinline__ void uv(const DrSeq& q, int i, double& u, double& v) {
-        const double2v r = *(const DR_GLOBAL double2u*)(static_cast<const double*>(q.a) + 2 * (size_t)i);
+        const double2v r = *(const MLD_BATCH_GLOBAL double2u*)(static_cast<const double*>(q.a) + 2 * (size_t)i);
         u = r.x, v = r.y;
     }
 };
@@ -111,7 +106,7 @@ __global__ __launch_bounds__(kBlock) void k_dr_pass(const DrSeq* __restrict__ de
     const int lane = (int)threadIdx.x & (kWave - 1), wave = (int)threadIdx.x >> 6;
     const int first = ((int)blockIdx.y * (kBlock / kWave) + wave) * kGroupsPerWave * kWave;  // the wavefront's first feature
     unsigned long long* __restrict__ gm = gm_all + (size_t)blockIdx.x * (size_t)groups_per_seq;
-    DR_GLOBAL const int32_t* type = as_global(q.type);
+    MLD_BATCH_GLOBAL const int32_t* type = as_global(q.type);
     double d[kGroupsPerWave];
     int t[kGroupsPerWave];
 #pragma unroll
@@ -144,13 +139,7 @@ __global__ __launch_bounds__(kBlock) void k_dr_pass(const DrSeq* __restrict__ de
         cnt += (int)__popcll(m);
     }
     if (lane == 0) wsum[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-#pragma unroll
-        for (int w = 0; w < kBlock / kWave; w++) s += wsum[w];
-        *as_global(cpre_all + (size_t)blockIdx.x * (size_t)(chunks_per_seq + 1) + blockIdx.y + 1) = s;
-    }
+    chunk_count(wsum, cpre_all, chunks_per_seq);
     if (type && threadIdx.x < kBins)
         *as_global(hist_all + ((size_t)blockIdx.x * (size_t)chunks_per_seq + blockIdx.y) * kBins + threadIdx.x) = bins[threadIdx.x];
 }
@@ -161,36 +150,12 @@ __global__ __launch_bounds__(kBlock) void k_dr_pass(const DrSeq* __restrict__ de
 __global__ __launch_bounds__(256) void k_dr_scan(const DrSeq* __restrict__ desc, int* __restrict__ cpre_all,
                                                 const int* __restrict__ hist_all, long long chunks_per_seq,
                                                 long long* __restrict__ report) {
-    __shared__ int wsum[256 / kWave];
     __shared__ long long part[kScanRows][kBins];
     const int n = desc[blockIdx.x].n;
     const bool typed = desc[blockIdx.x].type != nullptr;
     const int NC = (int)(((long long)n + kChunk - 1) / kChunk);
-    int* __restrict__ cpre = cpre_all + (size_t)blockIdx.x * (size_t)(chunks_per_seq + 1);
-    const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), w = tid >> 6;
-    if (tid == 0) cpre[0] = 0;
-    int carry = 0;
-    for (int c0 = 0; c0 < NC; c0 += 256) {  // (uniform)
-        const int c = c0 + tid;
-        const int v = c < NC ? cpre[c + 1] : 0;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int t = __shfl_up(incl, d);
-            if (lane >= d) incl += t;
-        }
-        if (lane == kWave - 1) wsum[w] = incl;
-        __syncthreads();
-        int off = carry, total = 0;
-#pragma unroll
-        for (int k = 0; k < 256 / kWave; k++) {
-            off += k < w ? wsum[k] : 0;
-            total += wsum[k];
-        }
-        if (c < NC) cpre[c + 1] = off + incl;
-        carry += total;
-        __syncthreads();
-    }
+    const int tid = (int)threadIdx.x;
+    const int carry = scan_chunk_counts(cpre_all + (size_t)blockIdx.x * (size_t)(chunks_per_seq + 1), NC);
     const int row = tid / kBins, bin = tid - row * kBins;
     if (row < kScanRows) {
         long long sum = 0;
@@ -232,32 +197,17 @@ __global__ __launch_bounds__(kBlock) void k_dr_write(const DrSeq* __restrict__ d
     const int G = (int)(((long long)n + kWave - 1) / kWave);
     const int g_mine = b * kGroupsPerChunk + lane;  // lanes 0..15: the masks of the block
     const unsigned long long mine = (lane < kGroupsPerChunk && g_mine < G) ? gm[g_mine] : 0ull;
-    const int pop = (int)__popcll(mine);
-    int incl = pop;
-#pragma unroll
-    for (int d = 1; d < kGroupsPerChunk; d <<= 1) {
-        const int t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    const int ahead = incl - pop;  // valid features of the block ahead of this lane's group
-    const unsigned mine_lo = (unsigned)mine, mine_hi = (unsigned)(mine >> 32);
-    DR_GLOBAL double* points = as_global(q.points);
-    DR_GLOBAL int32_t* feature = as_global(q.feature);
+    MLD_BATCH_GLOBAL double* points = as_global(q.points);
+    MLD_BATCH_GLOBAL int32_t* feature = as_global(q.feature);
     // (the cross-lane reads while every lane is here)
     unsigned lo[kGroupsPerWave], hi[kGroupsPerWave];
     int first_rank[kGroupsPerWave];
-#pragma unroll
-    for (int k = 0; k < kGroupsPerWave; k++) {
-        const int gl = wave * kGroupsPerWave + k;  // the group within the block
-        lo[k] = (unsigned)__shfl((int)mine_lo, gl);
-        hi[k] = (unsigned)__shfl((int)mine_hi, gl);
-        first_rank[k] = base + __shfl(ahead, gl);
-    }
+    group_ranks<kGroupsPerChunk>(mine, base, lane, wave, lo, hi, first_rank);
 #pragma unroll
     for (int k = 0; k < kGroupsPerWave; k++) {
         const unsigned long long m = ((unsigned long long)hi[k] << 32) | lo[k];
         if (!((m >> lane) & 1ull)) continue;  // (a set bit is a feature below n)
-        const int rank = first_rank[k] + (int)__builtin_amdgcn_mbcnt_hi(hi[k], __builtin_amdgcn_mbcnt_lo(lo[k], 0u));
+        const int rank = first_rank[k] + lane_rank(lo[k], hi[k]);
         if (rank >= q.capacity) continue;
         const int i = ((b * kGroupsPerChunk + wave * kGroupsPerWave + k) << 6) + lane;
         double u, v;
@@ -278,12 +228,9 @@ char g_error[512] = "";  // refusals without an object: mld_depth_reports_last_e
 struct mld_depth_reports : mld_batch::Object {
     int n_seq = 0;
     int64_t max_features = 0;
-    long long groups_per_seq = 0;  // 64-feature groups of max_features
-    long long chunks_per_seq = 0;  // 1024-feature chunks of max_features
     DrCam cam{};
-    unsigned long long* d_gm = nullptr;  // validity mask per group
-    int* d_cpre = nullptr;               // valid features ahead of every chunk (+ the total)
-    int* d_hist = nullptr;               // kBins counts per chunk
+    CompactScratch scratch;  // validity mask per group; valid features ahead of every chunk (+ the total)
+    int* d_hist = nullptr;   // kBins counts per chunk
     mld_batch::DescRing<DrSeq> ring;
 };
 
@@ -292,20 +239,16 @@ namespace {
 int allocate(mld_depth_reports* dr) {
     const int rc = dr->ring.allocate(dr, dr->n_seq);
     if (rc) return rc;
-    const size_t S = (size_t)dr->n_seq;
-    MLD_HIP(dr, hipMalloc((void**)&dr->d_gm, S * (size_t)dr->groups_per_seq * sizeof(unsigned long long)));
-    MLD_HIP(dr, hipMalloc((void**)&dr->d_cpre, S * (size_t)(dr->chunks_per_seq + 1) * sizeof(int)));
-    MLD_HIP(dr, hipMalloc((void**)&dr->d_hist, S * (size_t)dr->chunks_per_seq * kBins * sizeof(int)));
+    const int rs = dr->scratch.allocate(dr, dr->n_seq, dr->max_features, kChunk, 1);
+    if (rs) return rs;
+    MLD_HIP(dr, hipMalloc((void**)&dr->d_hist, (size_t)dr->n_seq * (size_t)dr->scratch.chunks_per_seq * kBins * sizeof(int)));
     return MLD_OK;
 }
 
 void free_own(mld_depth_reports* dr) {
-    if (dr->d_gm) (void)hipFree(dr->d_gm);
-    if (dr->d_cpre) (void)hipFree(dr->d_cpre);
+    dr->scratch.release();
     if (dr->d_hist) (void)hipFree(dr->d_hist);
 }
-
-bool misaligned(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
 // The shared body of the two entry points.  a / b: the coordinate tables (LoadF64: uv and none; LoadF32: u and v).
 template <typename Load>
@@ -371,14 +314,15 @@ int collect(mld_depth_reports* dr, const char* fn, const char* a_name, const voi
     if (rc) return rc;
     const unsigned chunks = (unsigned)((longest + kChunk - 1) / kChunk);  // (<= 16384)
     const unsigned Su = (unsigned)S;
+    const CompactScratch& cs = dr->scratch;
     if (chunks > 0)
-        hipLaunchKernelGGL(k_dr_pass<Load>, dim3(Su, chunks), dim3(kBlock), 0, dr->stream, dr->ring.d_desc, dr->d_gm,
-                           dr->groups_per_seq, dr->d_cpre, dr->d_hist, dr->chunks_per_seq);
-    hipLaunchKernelGGL(k_dr_scan, dim3(Su), dim3(256), 0, dr->stream, dr->ring.d_desc, dr->d_cpre, dr->d_hist, dr->chunks_per_seq,
+        hipLaunchKernelGGL(k_dr_pass<Load>, dim3(Su, chunks), dim3(kBlock), 0, dr->stream, dr->ring.d_desc, cs.d_gm,
+                           cs.groups_per_seq, cs.d_cpre, dr->d_hist, cs.chunks_per_seq);
+    hipLaunchKernelGGL(k_dr_scan, dim3(Su), dim3(256), 0, dr->stream, dr->ring.d_desc, cs.d_cpre, dr->d_hist, cs.chunks_per_seq,
                        reinterpret_cast<long long*>(report_out_dev));
     if (chunks > 0 && any_points)
-        hipLaunchKernelGGL(k_dr_write<Load>, dim3(Su, chunks), dim3(kBlock), 0, dr->stream, dr->ring.d_desc, dr->cam, dr->d_gm,
-                           dr->groups_per_seq, dr->d_cpre, dr->chunks_per_seq);
+        hipLaunchKernelGGL(k_dr_write<Load>, dim3(Su, chunks), dim3(kBlock), 0, dr->stream, dr->ring.d_desc, dr->cam, cs.d_gm,
+                           cs.groups_per_seq, cs.d_cpre, cs.chunks_per_seq);
     MLD_HIP(dr, hipGetLastError());
     return MLD_OK;
 }
@@ -402,8 +346,6 @@ mld_depth_reports* mld_depth_reports_create(mld_ctx* ctx, int n_seq, int64_t max
     auto init = [&](mld_depth_reports* dr) {
         dr->n_seq = n_seq;
         dr->max_features = max_features;
-        dr->groups_per_seq = (long long)((max_features + kWave - 1) / kWave);
-        dr->chunks_per_seq = (long long)((max_features + kChunk - 1) / kChunk);
         dr->cam.f = camera->focal_length;
         dr->cam.cu = camera->principal_point_x;
         dr->cam.cv = camera->principal_point_y;
@@ -419,10 +361,7 @@ const char* mld_depth_reports_last_error(const mld_depth_reports* dr) { return d
 int mld_depth_reports_collect_device(mld_depth_reports* dr, const double* const* uv, const double* const* depth,
                                      const int32_t* const* type, const int64_t* n_features, const int64_t* capacity,
                                      mld_depth_report* report_out_dev, double* const* points_out, int32_t* const* feature_out) {
-    if (!dr) {
-        std::snprintf(g_error, sizeof(g_error), "mld_depth_reports_collect_device: null object (dr)");
-        return MLD_ERR_INVALID_ARG;
-    }
+    if (!dr) return no_object(g_error, "mld_depth_reports_collect_device", "dr");
     return collect<LoadF64>(dr, "mld_depth_reports_collect_device", "uv", reinterpret_cast<const void* const*>(uv), nullptr,
                             reinterpret_cast<const void* const*>(depth), type, n_features, capacity, report_out_dev, points_out,
                             feature_out);
@@ -432,10 +371,7 @@ int mld_depth_reports_collect_tracks_device(mld_depth_reports* dr, const float* 
                                             const float* const* depth, const int32_t* const* type, const int64_t* n_features,
                                             const int64_t* capacity, mld_depth_report* report_out_dev, double* const* points_out,
                                             int32_t* const* feature_out) {
-    if (!dr) {
-        std::snprintf(g_error, sizeof(g_error), "mld_depth_reports_collect_tracks_device: null object (dr)");
-        return MLD_ERR_INVALID_ARG;
-    }
+    if (!dr) return no_object(g_error, "mld_depth_reports_collect_tracks_device", "dr");
     return collect<LoadF32>(dr, "mld_depth_reports_collect_tracks_device", "u", reinterpret_cast<const void* const*>(u),
                             reinterpret_cast<const void* const*>(v), reinterpret_cast<const void* const*>(depth), type, n_features,
                             capacity, report_out_dev, points_out, feature_out);

@@ -22,7 +22,8 @@
 // The road fit itself is not repeated: its depth is the depth path's business.
 //
 // This translation unit uses the depth path through its public C-ABI only (mld_get_stream) and shares no internals with
-// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h).  The records are nevertheless bit for bit what
+// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h; as_global, V3 and the size limits:
+// ../batch/mld_batch_device.h).  The records are nevertheless bit for bit what
 // that path and the CPU restatement compute (tests/test_feature_traces_gpu.py pins that): the device functions below
 // are copies, operation for operation, of that path's arithmetic (plane_through, viewing_ray, intersect, the histogram,
 // the triangle search, the thresholds), Tinv and Kinv are formed as mld_create forms them, and this unit is compiled
@@ -36,15 +37,15 @@
 #include <string>
 
 #include "../batch/mld_batch_object.h"
+#include "../batch/mld_batch_device.h"
 #include "../../../include/mld.h"
 
 namespace {
 
-constexpr int kWave = 64;
+using namespace mld_batch;
+
 constexpr int kMaxCells = 1024;        // cells of the widest window an object accepts = entries of a list in LDS
 constexpr int kMaxGridY = 65535;       // features of a sequence beyond it share blocks (grid-stride)
-constexpr int64_t kMaxFeatures = 16777216;
-constexpr int64_t kMaxPoints = 8388607;
 constexpr int kNone = 0x7fffffff;      // "no candidate yet" of the (value, id) reductions
 constexpr double kDblMax = 1.7976931348623157e308;
 
@@ -84,13 +85,6 @@ struct TrCalib {
     int32_t minCount, useHist, thrG_en, thrG_mode, thrL_en, thrL_mode, thrL_type, useTriMax, checkPlanar, cutBehind, useRoad;
 };
 
-// The arrays of a descriptor are GPU memory: said to the compiler, their accesses are global_* instead of flat_*.
-#define TR_GLOBAL __attribute__((address_space(1)))
-template <typename T>
-__device__ __forceinline__ TR_GLOBAL T* as_global(T* p) {
-    return (TR_GLOBAL T*)p;
-}
-
 __device__ __forceinline__ int prefix_count(unsigned long long m) {
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
@@ -110,9 +104,6 @@ __device__ __forceinline__ void reduce_best(double& v, int& id) {
     }
 }
 
-struct V3 {
-    double x, y, z;
-};
 // Eigen fixed-size Vector3d semantics: redux over three is func(x0, func(x1, x2))
 __device__ __forceinline__ V3 vsub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ V3 vadd(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
@@ -278,7 +269,7 @@ struct Lists {
 // Bounds in f64 with (int) truncation, as there.  A cell whose map value or index lies outside the arrays counts as empty
 // and sets `bad`.  row: where the visible indices go (up to list_cap of them), or null.
 __device__ __forceinline__ int gather_window(const TrCalib& c, const TrSeq& q, double u, double v, double halfX, double halfY,
-                                             const Lists& L, int lane, TR_GLOBAL int32_t* row, int list_cap, bool& bad) {
+                                             const Lists& L, int lane, MLD_BATCH_GLOBAL int32_t* row, int list_cap, bool& bad) {
     if (!(isfinite(u) && isfinite(v))) return 0;  // reference: undefined behaviour (int cast of NaN)
     double a;
     a = u - halfX;
@@ -295,9 +286,9 @@ __device__ __forceinline__ int gather_window(const TrCalib& c, const TrSeq& q, d
     if (x0 < 0 || y0 < 0 || x1 >= c.W || y1 >= c.H) return 0;  // unreachable for finite features
     if ((long long)nx * (long long)ny > (long long)c.cap) return 0;  // unreachable: the object's bound on the window
     const int ncell = nx * ny;
-    const TR_GLOBAL int32_t* map = as_global(q.map);
-    const TR_GLOBAL int32_t* index = as_global(q.index);
-    const TR_GLOBAL double* cam = as_global(q.cam);
+    const MLD_BATCH_GLOBAL int32_t* map = as_global(q.map);
+    const MLD_BATCH_GLOBAL int32_t* index = as_global(q.index);
+    const MLD_BATCH_GLOBAL double* cam = as_global(q.cam);
     int k = 0;
     bool badl = false;
     for (int base = 0; base < ncell; base += kWave) {
@@ -527,7 +518,7 @@ __device__ __forceinline__ void trace_feature(const TrCalib& c, const TrSeq& q, 
         } else {
             n_seg = ks;
             if (q.seg) {
-                TR_GLOBAL int32_t* out = as_global(q.seg) + row;
+                MLD_BATCH_GLOBAL int32_t* out = as_global(q.seg) + row;
                 const int m = ks < list_cap ? ks : list_cap;
                 for (int i = lane; i < m; i += kWave) out[i] = L.pos[i];
             }
@@ -583,7 +574,7 @@ __device__ __forceinline__ void trace_feature(const TrCalib& c, const TrSeq& q, 
             road_state = MLD_TRACE_ROAD_FEW_NEIGHBOURS;
         } else {
             // CalculateDepthSegmentationPlane (:782-900)
-            const TR_GLOBAL uint32_t* mask = as_global(q.mask);
+            const MLD_BATCH_GLOBAL uint32_t* mask = as_global(q.mask);
             bool anyFar = false;
             int kk = 0;
             for (int b = 0; b < n_road; b += kWave) {
@@ -615,7 +606,7 @@ __device__ __forceinline__ void trace_feature(const TrCalib& c, const TrSeq& q, 
                 n_inl = kk;
                 road_state = kk < 3 ? MLD_TRACE_ROAD_FEW_INLIERS : MLD_TRACE_ROAD_FIT;  // :827-829
                 if (q.road_inl) {
-                    TR_GLOBAL int32_t* out = as_global(q.road_inl) + row;
+                    MLD_BATCH_GLOBAL int32_t* out = as_global(q.road_inl) + row;
                     const int m = kk < list_cap ? kk : list_cap;
                     for (int i = lane; i < m; i += kWave) out[i] = L.pos[i];
                 }
@@ -808,8 +799,6 @@ namespace {
 
 void free_own(mld_feature_traces*) {}
 
-bool misaligned(const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 // Both collect calls: u_tab = uv (v_tab null) or u, v.
 template <bool kTracks>
 int collect(mld_feature_traces* ft, const char* fn, const void* const* u_tab, const float* const* v_tab, const int64_t* n_features,
@@ -817,10 +806,7 @@ int collect(mld_feature_traces* ft, const char* fn, const void* const* u_tab, co
             const int64_t* n_points, const float* coeffs, const uint32_t* const* mask_dev, int list_capacity,
             mld_feature_trace* const* trace_out, int32_t* const* nb_out, int32_t* const* seg_out, int32_t* const* road_out,
             int32_t* const* road_inl_out) {
-    if (!ft) {
-        std::snprintf(g_error, sizeof(g_error), "%s: null object (ft)", fn);
-        return MLD_ERR_INVALID_ARG;
-    }
+    if (!ft) return no_object(g_error, fn, "ft");
     auto refuse = [&](int code, const char* text) { return fail(ft, code, (std::string(fn) + ": " + text).c_str()); };
 #define TR_REFUSE(text) return refuse(MLD_ERR_INVALID_ARG, text)
     if (!u_tab) TR_REFUSE(kTracks ? "null table u" : "null table uv");

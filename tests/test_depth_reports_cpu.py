@@ -139,7 +139,7 @@ def test_the_reports_are_a_translation_unit_of_their_own():
     not know of it."""
     csrc = ROOT / "mono_lidar_depth_amd" / "csrc"
     text = (csrc / "reports" / "mld_depth_reports.hip").read_text()
-    assert re.findall(r'#include\s+"([^"]+)"', text) == ["../batch/mld_batch_object.h"]
+    assert re.findall(r'#include\s+"([^"]+)"', text) == ["../batch/mld_batch_object.h", "../batch/mld_batch_device.h"]
     assert "mld_device.h" not in text and "mld_diag.h" not in text
     for name in ("DescRing<", "create_object<", "destroy_object("):
         assert name in text, name

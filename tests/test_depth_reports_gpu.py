@@ -240,6 +240,17 @@ def test_ragged_calls(est, S, form):
     verify(run(est, seqs, max_features=5000), f"{form} S={S}")
 
 
+LONG = (65537, 262145, 1)  # 65 chunks: the scan's second wavefront; 257: its second round, the last chunk of one feature
+
+
+def test_long_sequences_whose_chunk_counts_leave_the_first_wavefront_and_the_first_round_of_the_scan(est):
+    """One call on an object of max_features 262 145: the prefix over the chunk counts crosses from wavefront 0 to
+    wavefront 1 (65 chunks) and carries into a second round of 256 chunks (257 chunks); the histogram sum likewise."""
+    seqs = [make_inputs("f64", n, 100 + n) for n in LONG]
+    assert all(0 < restate(q)[2].size < q["n"] for q in seqs[:2])
+    verify(run(est, seqs, max_features=262145), "long")
+
+
 @pytest.mark.parametrize("form", FORMS)
 @pytest.mark.parametrize("layout", ["all", "none", "last"])
 def test_layouts(est, layout, form):

@@ -186,7 +186,8 @@ def test_the_traces_are_a_translation_unit_of_their_own():
     sources do not know of it; one kernel with a stable name."""
     csrc = ROOT / "mono_lidar_depth_amd" / "csrc"
     text = (csrc / "traces" / "mld_feature_traces.hip").read_text()
-    assert re.findall(r'#include\s+"([^"]+)"', text) == ["../batch/mld_batch_object.h", "../../../include/mld.h"]
+    assert re.findall(r'#include\s+"([^"]+)"', text) == ["../batch/mld_batch_object.h", "../batch/mld_batch_device.h",
+                                                           "../../../include/mld.h"]
     assert "mld_device.h" not in text and "mld_diag.h" not in text
     assert "asm" not in re.sub(r"//.*", "", text)
     assert re.findall(r"__global__[^\n]*\bvoid (\w+)\(", text) == ["k_feature_trace"]

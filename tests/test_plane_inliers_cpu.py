@@ -121,7 +121,7 @@ def test_the_inliers_are_a_translation_unit_of_their_own():
     """In planes/, on the shared batch header only, linked into both libraries; the depth path's sources do not know of it."""
     csrc = ROOT / "mono_lidar_depth_amd" / "csrc"
     text = (csrc / "planes" / "mld_plane_inliers.hip").read_text()
-    assert re.findall(r'#include\s+"([^"]+)"', text) == ["../batch/mld_batch_object.h"]
+    assert re.findall(r'#include\s+"([^"]+)"', text) == ["../batch/mld_batch_object.h", "../batch/mld_batch_device.h"]
     assert "mld_device.h" not in text and "mld_diag.h" not in text
     assert "asm" not in re.sub(r"//.*", "", text)
     mk = (csrc / "Makefile").read_text()

@@ -268,6 +268,22 @@ def test_the_sizes_in_one_ragged_call_equal_the_restatement(est, stride, shifted
     pi.close()
 
 
+LONG = (65537, 262145, 1)  # 65 chunks: the scan's second wavefront; 257: its second round, the last chunk of one point
+
+
+@pytest.mark.parametrize("use", [False, True])
+def test_long_sequences_whose_chunk_counts_leave_the_first_wavefront_and_the_first_round_of_the_scan(est, use):
+    """One call on an object of max_points 262 145: the prefixes over the chunk counts cross from wavefront 0 to wavefront
+    1 (65 chunks) and carry into a second round of 256 chunks (257 chunks) - with the filter on, both of them."""
+    clouds = [size_cloud(n) for n in LONG]
+    got = run(est, params(use), clouds, [make_mask(n, "half") for n in LONG], max_points=262145)
+    for n, g in zip(LONG, got):
+        want = want_size(n, "half", use)
+        if n > 1:
+            assert 0 < want["n_cloud"] < n and (want["n_cloud"] < want["n_inliers"]) == use
+        check(g, want, n, f"long n={n} filter={use}")
+
+
 def filter_cloud():
     """Camera = lidar frame (SMALL_T): x_cam is the record's x.  Points at +0.0, -0.0, +-2, just beyond, NaN, inf."""
     xs = [0.0, -0.0, 2.0, -2.0, np.nextafter(np.float32(2.0), np.float32(3.0)), 1.5, -1.5, np.nan, np.inf, -np.inf, 9.0, 1e-30]

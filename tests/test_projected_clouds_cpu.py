@@ -118,7 +118,7 @@ def test_the_clouds_are_a_translation_unit_of_their_own():
     """In clouds/, on the public header only, linked into both libraries; the depth path's sources do not know of it."""
     csrc = ROOT / "mono_lidar_depth_amd" / "csrc"
     text = (csrc / "clouds" / "mld_projected_clouds.hip").read_text()
-    assert re.findall(r'#include\s+"([^"]+)"', text) == ["../batch/mld_batch_object.h"]
+    assert re.findall(r'#include\s+"([^"]+)"', text) == ["../batch/mld_batch_object.h", "../batch/mld_batch_device.h"]
     assert "mld_device.h" not in text and "mld_diag.h" not in text
     mk = (csrc / "Makefile").read_text()
     link_lines = [ln for ln in mk.splitlines() if "-shared" in ln]

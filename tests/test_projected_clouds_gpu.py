@@ -227,6 +227,20 @@ def test_the_sizes_in_one_ragged_call_equal_the_oracle(est, stride, offset):
         check(g, expected(c, key=("sizes", n)), n, n, f"ragged n={n}")
 
 
+LONG = (65537, 262145, 1)  # 65 chunks: the scan's second wavefront; 257: its second round, the last chunk of one point
+
+
+def test_long_sequences_whose_chunk_counts_leave_the_first_wavefront_and_the_first_round_of_the_scan(est):
+    """One call on an object of max_points 262 145: the prefix over the chunk counts crosses from wavefront 0 to
+    wavefront 1 (65 chunks) and carries into a second round of 256 chunks (257 chunks)."""
+    clouds = [random_cloud(n, 100 + n) for n in LONG]
+    got = run(est, kitti_camera(), clouds, max_points=262145)
+    for n, c, g in zip(LONG, clouds, got):
+        want = expected(c, key=("sizes", n))
+        assert n == 1 or 0 < want["nvis"] < n
+        check(g, want, n, n, f"long n={n}")
+
+
 def boundary_cloud():
     """Camera 64 x 64, f = 64, cu = cv = 32, identity transform: u = 64 x / z + 32, v = 64 y / z + 32, exactly."""
     nan, inf = np.nan, np.inf

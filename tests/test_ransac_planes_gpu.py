@@ -300,6 +300,20 @@ def test_the_z_pass_through_window(est):
     assert 0 < got[6][1] <= 6000
 
 
+def test_long_sequences_whose_chunk_counts_leave_the_first_wavefront_and_the_first_round_of_the_scan(est):
+    """One call on an object of max_points 262 145 with the z window on: the prefix over the chunk counts of the
+    pass-through crosses from wavefront 0 to wavefront 1 (65 537 points: 65 chunks) and carries into a second round of 256
+    chunks (262 145 points: 257 chunks, the last of one point); the sample is drawn through that prefix."""
+    P = capi.params_c0().replace(**WINDOW)
+    shapes = [(65537, 20001), (262145, 80003), (1, 1)]
+    clouds = [window_cloud(n, k, 300 + i) for i, (n, k) in enumerate(shapes)]
+    seeds = [70 + i for i in range(len(clouds))]
+    got = run(est, P, clouds, seeds, max_points=262145)
+    check_all(P, clouds, seeds, got, "long window")
+    for (n, k), g in zip(shapes, got):
+        assert g[4] == k and g[3] == (1 if k < 3 else 0), (n, k, g[3], g[4])
+
+
 def test_a_window_that_holds_nothing_and_clouds_of_nan(est):
     none = capi.params_c0().replace(ransac_plane_min_z=5.0, ransac_plane_max_z=6.0)
     clouds = [plane_cloud(300, 1), plane_cloud(7000, 2)]

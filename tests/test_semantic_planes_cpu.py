@@ -107,7 +107,7 @@ def test_the_planes_are_a_translation_unit_of_their_own():
     csrc = ROOT / "mono_lidar_depth_amd" / "csrc"
     text = (csrc / "planes" / "mld_semantic_planes.hip").read_text()
     # public header only: through the shared header of the batch objects, which itself includes nothing else of the project
-    assert re.findall(r'#include\s+"([^"]+)"', text) == ["../batch/mld_batch_object.h"]
+    assert re.findall(r'#include\s+"([^"]+)"', text) == ["../batch/mld_batch_object.h", "../batch/mld_batch_device.h"]
     shared = (csrc / "batch" / "mld_batch_object.h").read_text()
     assert re.findall(r'#include\s+"([^"]+)"', shared) == ["../../../include/mld.h"]
     for src in (text, shared):
