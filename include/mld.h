@@ -469,6 +469,17 @@ int mld_tracklets_frame(mld_ctx* ctx, int slot_cur, int slot_last, const void* p
  *                                       NEW tracks' previous features on the previous frame (have_last == 0: no previous
  *                                       clouds yet, those depths are -1) -> float32 scatter; arrays of n_seq device
  *                                       pointers / counts, indexing and meaning per sequence as mld_tracklets_depth_device
+ *   mld_tracklets_depths_lanes_device   the same with have_last[s] (host, n_seq flags) per sequence, for sequences that
+ *                                       start at different frames: where have_last[s] == 0 nothing of the previous-bank
+ *                                       slot of s is read and the new tracks of s get d_last = -1 / MLD_Unspecified - what
+ *                                       the scalar flag does for all sequences.  Equal flags: the scalar call.  Mixed
+ *                                       flags: two launch sets of the scalar call, the sequences with a previous frame,
+ *                                       then those without, each with the other group's track counts at zero.
+ *                                       DEVIATION: with mixed flags the previous-bank slot of EVERY sequence is checked
+ *                                       as the scalar call checks it (a cloud, and a plane where the parameters ask for
+ *                                       one), also where have_last[s] == 0 and nothing of it is read: such a slot must
+ *                                       have held some frame (TrackletBatch gives a slot that never did the current
+ *                                       one).  The flags are consumed before the call returns.
  * Asynchronous on the context's stream; per-sequence results equal n_seq single-sequence calls.
  */
 int mld_set_clouds_planes_range_device(mld_ctx* ctx, int first_slot, int n_slots, const void* const* pts_dev,
@@ -478,6 +489,10 @@ int mld_tracklets_depths_device(mld_ctx* ctx, int n_seq, int bank_cur, int have_
                                 const float* const* v_new, const float* const* u_old, const float* const* v_old,
                                 const uint8_t* const* is_new, const int64_t* n_tracks, float* const* d_cur_out,
                                 float* const* d_last_out, int32_t* const* type_cur_out, int32_t* const* type_last_out);
+int mld_tracklets_depths_lanes_device(mld_ctx* ctx, int n_seq, int bank_cur, const uint8_t* have_last, const float* const* u_new,
+                                      const float* const* v_new, const float* const* u_old, const float* const* v_old,
+                                      const uint8_t* const* is_new, const int64_t* n_tracks, float* const* d_cur_out,
+                                      float* const* d_last_out, int32_t* const* type_cur_out, int32_t* const* type_last_out);
 
 /*
  * The tracklet map of the batched layer, resident on the GPU — `_trackletMap` (std::map<int, feature_tracking::Tracklet>,
@@ -489,9 +504,14 @@ int mld_tracklets_depths_device(mld_ctx* ctx, int n_seq, int bank_cur, int have_
  *   mld_tracks_export_device  convert_tracklets_to_matches_msg (:209-259): the stored tracks in message order
  *   mld_tracks_export_packed_device  the same tracks back to back, every track with exactly its stored entries, and
  *                             the offsets at which they start (what the message holds: `curTracklet.size()` points each)
+ *   mld_tracks_import_packed_device  the inverse of the packed export: the committed frame of the selected sequences
+ *                             replaced by given tracks, as if a fresh TrackletDepthModule had been brought to that state
+ *                             (the reference has no checkpoint / resume: SURVEY 5); mld_tracks_reset_device: by no tracks
  *   mld_tracks_counts         the counters those functions return ((new, old) :60/:168, (success, failed) :258)
  *   mld_tracklets_step_device begin -> mld_tracklets_depths_device with the store's masks -> commit: process()'s whole
  *                             track side (:286-347) as ONE asynchronous chain; ids + features in, depths + histories out
+ *   mld_tracklets_step_lanes_device  the same for sequences that start, restart and resume independently: have_last
+ *                             and restart per sequence
  * The store is bound to a context: it lives on that context's device and every call is asynchronous on that context's
  * stream (mld_tracks_counts synchronises).  The host tables (arrays of n_seq device pointers / counts) are consumed
  * before a call returns: a caller may queue many frames ahead of the device and reuse its host arrays.  The device
@@ -507,8 +527,8 @@ int mld_tracklets_depths_device(mld_ctx* ctx, int n_seq, int bank_cur, int have_
  *     n_seq * (max_tracks * (12 * max_history + 45) + 16 * cap + 132 + 12 * ceil(max_tracks / 256))
  *   (histories 12 * max_history per track: 0.49 GB of 0.74 GB for 256 sequences x 10 000 tracks x 16 entries; 4 of the 45
  *   bytes per track and the last term are the scratch of the packed export's scan: length and ring head per track, a
- *   32-bit sum and a 64-bit base per block of 256 tracks), plus
- *   16 * 96 * n_seq bytes of pinned host memory.
+ *   32-bit sum and a 64-bit base per block of 256 tracks), plus max_tracks bytes once (the all-zero mask of
+ *   mld_tracklets_step_lanes_device) and 16 * 96 * n_seq bytes of pinned host memory.
  *   Returns NULL on failure with the reason in *status_out (optional) and the text in mld_tracks_last_error(NULL).
  *   Destroy the store before its context.
  *
@@ -541,6 +561,32 @@ int mld_tracklets_depths_device(mld_ctx* ctx, int n_seq, int bank_cur, int have_
  *   capacity[s] = n_tracks[s] * max_history never truncates.  A sequence without tracks needs no arrays and gets nothing
  *   written; a capacity of 0 needs no fp_out[s].  Any other null array of a sequence with tracks is refused.  Asynchronous, no synchronisation, no host read of device data, nothing allocated per call.
  *
+ * mld_tracks_import_packed_device: per sequence s with select[s] != 0 (select: host, n_seq flags; NULL: every sequence)
+ *   the committed frame is replaced by the n_tracks[s] given tracks in the given (message) order: track i has id
+ *   ids[s][i] and the entries fp[s][3 * (offsets[s][i] + e) ..], e < L = offsets[s][i+1] - offsets[s][i], newest first -
+ *   the layout mld_tracks_export_packed_device writes (n + 1 int64 offsets, (u, v, d) float32 entries; device arrays, the
+ *   tables of n_seq pointers / counts on the host).  Entries are stored bit for bit (no truncation to int: the caller
+ *   hands in what an export produced), so that both exports and the counts of the store equal the source's and the
+ *   frames that follow equal an uninterrupted run; the source may have another max_tracks / max_history, context or GPU.
+ *   Sequences with select[s] == 0 are not touched in any way and their table entries may be NULL.  n_tracks[s] == 0
+ *   empties the sequence (its arrays may be NULL).
+ *   DEVIATIONS and bounds: L > max_history keeps the newest max_history entries (the cap of mld_tracks_create).
+ *   n_entries[s] (host) = the entries fp[s] holds: offsets are clamped to [0, n_entries[s]] on the device, a decreasing pair
+ *   gives length 0, nothing at or beyond n_entries[s] is read; a track of length 0 is stored with length 0 and the next
+ *   commit pushes onto it.  offsets[s] always holds n_tracks[s] + 1 entries.  A repeated id follows the rule of
+ *   mld_tracks_commit_device: one occurrence is stored (which one is unspecified), the others are counted and export the
+ *   stored occurrence's history.  mld_tracks_counts of an imported sequence: [1] = tracks stored by the import, [2] = 0,
+ *   [0] = [1] + [2], [3] / [4] over the stored entries as always, [5] = repeated ids.  A begun, uncommitted frame is
+ *   abandoned for ALL sequences, as a second begin abandons it (the frame a failed step left behind included): a commit
+ *   without a new begin returns MLD_ERR_NOT_INITIALIZED.  n_tracks[s] > max_tracks returns MLD_ERR_CAPACITY; a null table,
+ *   a null array of a selected sequence with tracks (fp[s] only where n_entries[s] > 0), a negative count or n_entries
+ *   MLD_ERR_INVALID_ARG; everything is checked before anything is queued or any host state changes.  Asynchronous, no
+ *   synchronisation, no host read of device data, nothing allocated per call; the ids are read by this call only.  Two
+ *   launches behind the descriptor upload, flat over the selected sequences: the reset (table cleared, row pool as created)
+ *   and insert + fill.
+ *
+ * mld_tracks_reset_device: the import of no tracks into the selected sequences (select == NULL: all): one launch.
+ *
  * mld_tracks_counts: counts_out = n_seq x 6 int64 of the last committed frame: [0] live tracks, [1] created this frame,
  *   [2] updated this frame, [3] stored features with d >= 0, [4] the other stored features, [5] repeated ids.
  *
@@ -548,6 +594,17 @@ int mld_tracklets_depths_device(mld_ctx* ctx, int n_seq, int bank_cur, int have_
  *   `tr` must have been created on `ctx` with the same n_seq.  The caller supplies feature_points[1] (u_old / v_old) for
  *   every track; it is read only where the track turns out to be new.  d_last_out is written only there.  No
  *   synchronisation, no host read of device data.
+ *
+ * mld_tracklets_step_lanes_device: mld_tracklets_step_device with have_last[s] per sequence (host, n_seq flags, as
+ *   mld_tracklets_depths_lanes_device) and restart (host, n_seq flags; NULL: none).  restart[s] != 0 is the construction
+ *   of a new TrackletDepthModule for sequence s: its store is emptied ahead of the look-up (mld_tracks_reset_device of the
+ *   restarting sequences: one more launch, only when there is one), have_last[s] counts as 0, every id of s is new - ids
+ *   the sequence held a frame ago included - and its d_last is -1 (tracklet_depth_module.cpp:93-96).  With restart == NULL
+ *   and equal flags the launches and results are those of mld_tracklets_step_device.  A step with mixed flags makes the
+ *   same ONE launch set of the depth call with have_last = 1 and hands it an all-zero mask for the sequences without a
+ *   previous frame, so that none of their previous features is evaluated; one more launch then writes their new tracks'
+ *   d_last = -1 / MLD_Unspecified.  The previous-bank slots are checked as stated at mld_tracklets_depths_lanes_device.  What the begin refuses is refused
+ *   before a sequence is emptied; a depth call that fails afterwards leaves the restarted sequences empty.
  */
 typedef struct mld_tracks mld_tracks;
 mld_tracks* mld_tracks_create(mld_ctx* ctx, int n_seq, int64_t max_tracks, int max_history, int* status_out);
@@ -559,11 +616,19 @@ int mld_tracks_commit_device(mld_tracks* tr, const float* const* u_new, const fl
 int mld_tracks_export_device(mld_tracks* tr, float* const* fp_out, int32_t* const* len_out);
 int mld_tracks_export_packed_device(mld_tracks* tr, float* const* fp_out, const int64_t* capacity,
                                     int64_t* const* offsets_out);
+int mld_tracks_import_packed_device(mld_tracks* tr, const uint8_t* select, const int32_t* const* ids, const int64_t* n_tracks,
+                                    const int64_t* const* offsets, const float* const* fp, const int64_t* n_entries);
+int mld_tracks_reset_device(mld_tracks* tr, const uint8_t* select);
 int mld_tracks_counts(mld_tracks* tr, int64_t* counts_out);
 int mld_tracklets_step_device(mld_ctx* ctx, mld_tracks* tr, int bank_cur, int have_last, const int32_t* const* ids,
                               const float* const* u_new, const float* const* v_new, const float* const* u_old,
                               const float* const* v_old, const int64_t* n_tracks, float* const* d_cur_out,
                               float* const* d_last_out, int32_t* const* type_cur_out, int32_t* const* type_last_out);
+int mld_tracklets_step_lanes_device(mld_ctx* ctx, mld_tracks* tr, int bank_cur, const uint8_t* have_last, const uint8_t* restart,
+                                    const int32_t* const* ids, const float* const* u_new, const float* const* v_new,
+                                    const float* const* u_old, const float* const* v_old, const int64_t* n_tracks,
+                                    float* const* d_cur_out, float* const* d_last_out, int32_t* const* type_cur_out,
+                                    int32_t* const* type_last_out);
 
 /*
  * Per-track semantic labels for a batch — matches_conversion_ros_tool's `semantic_labels` node, assignLabels

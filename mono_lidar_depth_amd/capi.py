@@ -227,6 +227,8 @@ _SIGNATURES = [
                                                      _P(C.c_float), _P(C.c_void_p)]),
     ("mld_tracklets_depths_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [_P(C.c_void_p)] * 5 +
      [_P(C.c_int64)] + [_P(C.c_void_p)] * 4),
+    ("mld_tracklets_depths_lanes_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_uint8)] + [_P(C.c_void_p)] * 5 +
+     [_P(C.c_int64)] + [_P(C.c_void_p)] * 4),
     ("mld_tracks_create", C.c_void_p, [C.c_void_p, C.c_int, C.c_int64, C.c_int, _P(C.c_int)]),
     ("mld_tracks_destroy", None, [C.c_void_p]),
     ("mld_tracks_last_error", C.c_char_p, [C.c_void_p]),
@@ -234,9 +236,14 @@ _SIGNATURES = [
     ("mld_tracks_commit_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 6),
     ("mld_tracks_export_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p)]),
     ("mld_tracks_export_packed_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64), _P(C.c_void_p)]),
+    ("mld_tracks_import_packed_device", C.c_int, [C.c_void_p, _P(C.c_uint8), _P(C.c_void_p), _P(C.c_int64), _P(C.c_void_p),
+                                                  _P(C.c_void_p), _P(C.c_int64)]),
+    ("mld_tracks_reset_device", C.c_int, [C.c_void_p, _P(C.c_uint8)]),
     ("mld_tracks_counts", C.c_int, [C.c_void_p, _P(C.c_int64)]),
     ("mld_tracklets_step_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [_P(C.c_void_p)] * 5 +
      [_P(C.c_int64)] + [_P(C.c_void_p)] * 4),
+    ("mld_tracklets_step_lanes_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_uint8), _P(C.c_uint8)] +
+     [_P(C.c_void_p)] * 5 + [_P(C.c_int64)] + [_P(C.c_void_p)] * 4),
     ("mld_labels_create", C.c_void_p, [C.c_void_p, C.c_int, _P(C.c_int)]),
     ("mld_labels_destroy", None, [C.c_void_p]),
     ("mld_labels_last_error", C.c_char_p, [C.c_void_p]),

@@ -32,6 +32,11 @@
 //                      table with atomicCAS, then pushes its entries
 //   k_tracks_export / k_tracks_count   read-only
 //   k_tracks_pack_sums / _scan / _write   read-only: the packed export, tracks back to back with offsets (below)
+//   k_tracks_reset / k_tracks_import      the packed import, the inverse of that export, for selected sequences: the
+//                      committed table and the pool as created, then insert + fill (at the kernels); the reset alone
+//                      empties sequences (mld_tracks_reset_device, the restart of mld_tracklets_step_lanes_device)
+//   k_tracks_no_previous   a lanes step with mixed flags: d_last = -1 for the new tracks of the sequences without a
+//                      previous frame, which the depth call saw with an all-zero mask (at mld_tracklets_step_lanes_device)
 // Rows are released before they are taken and never in the same kernel, so max_tracks rows per sequence sustain
 // max_tracks tracks per frame at any churn, and the stack needs no ABA care.
 //
@@ -76,17 +81,24 @@ struct TrSeq {
     const float* d_cur;
     union {
         const float* d_last;
-        int64_t capacity;  // mld_tracks_export_packed_device: entries fp_out holds
+        float* d_last_w;    // mld_tracklets_step_lanes_device: d_last_out of a sequence without a previous frame
+        int64_t capacity;   // mld_tracks_export_packed_device: entries fp_out holds
+        int64_t n_entries;  // mld_tracks_import_packed_device: entries fp_in holds
     };
-    float* fp_out;
     union {
-        int32_t* len_out;      // mld_tracks_export_device
-        int64_t* offsets_out;  // mld_tracks_export_packed_device
+        float* fp_out;
+        const float* fp_in;  // mld_tracks_import_packed_device
+    };
+    union {
+        int32_t* len_out;           // mld_tracks_export_device (k_tracks_no_previous: type_last_out)
+        int64_t* offsets_out;       // mld_tracks_export_packed_device
+        const int64_t* offsets_in;  // mld_tracks_import_packed_device
     };
     int32_t n;          // tracks of the frame the call works on
     int32_t n_prev;     // tracks of the committed frame (release pass)
     int32_t blk0;       // first block of the sequence in a launch over n (export: over n * max_history)
-    int32_t blk0_prev;  // the same for the release pass (at least one block per sequence)
+    int32_t blk0_prev;  // the same for the release pass (at least one block per sequence; reset: over the table's
+                        // slots, and none for a sequence that is not selected)
 };
 static_assert(sizeof(TrSeq) == 96, "96 bytes per sequence (DESIGN.md)");
 
@@ -434,6 +446,129 @@ __global__ __launch_bounds__(kBlock) void k_tracks_pack_write(TrDev T, const TrS
     }
 }
 
+// ---- the packed import: the inverse of the packed export ----
+
+// The selected sequences as mld_tracks_create left them: the committed table without an id, every row on the free stack
+// (free_rows[p] = p, top = max_tracks), the frame counters at zero.  Flat over (selected sequence, 256 table slots) -
+// cap >= max_tracks, so the same index walks the stack.  Independent of what the sequence held; the other table is
+// empty already (the store's invariant).
+__global__ __launch_bounds__(kBlock) void k_tracks_reset(TrDev T, const TrSeq* __restrict__ desc, int cur) {
+    const int s = seq_of_block<true>(desc, T.n_seq, (int)blockIdx.x);
+    const TrSeq& q = desc[s];
+    const uint32_t j = (uint32_t)((int)blockIdx.x - q.blk0_prev) * kBlock + threadIdx.x;
+    if (j >= T.cap) return;
+    T.table[((size_t)cur * T.n_seq + s) * T.cap + j] = 0ull;
+    if (j < (uint32_t)T.M) T.free_rows[(size_t)s * T.M + j] = (int32_t)j;
+    if (j < 4) T.cnt[(size_t)s * 4 + j] = 0;
+    if (j == 0) T.top[s] = T.M;
+}
+
+// Insert and fill in one kernel over blocks of 256 tracks of the selected sequences (after k_tracks_reset).
+//   insert  one thread per track.  The pool is as created, so the n pops are known without atomics: track i takes
+//           free_rows[M - 1 - i] = row M - 1 - i and thread 0 leaves top = M - n.  The slot is claimed in the COMMITTED
+//           table as k_tracks_commit claims it; a repeated id that lost keeps slot -1, the winner's row and its own row
+//           in dup_row (the next commit's k_tracks_release walks row / slot / dup_row of every i < n and hands it back).
+//           Offsets are clamped to [0, n_entries]; a decreasing pair is a track without entries; head = 0,
+//           len = min(L, H): the newest entries stay.
+//   fill    the mirror of k_tracks_pack_write: the stored lengths (0 for a loser) are prefix-summed in LDS, one thread
+//           per entry finds its track by binary search and moves 12 bytes from the track's run to its row - runs of
+//           consecutive tracks are consecutive in fp_in wherever an export wrote them.  A thread knows whether its track
+//           won as soon as its own atomicCAS returns, so the fill needs no second kernel.
+__global__ __launch_bounds__(kBlock) void k_tracks_import(TrDev T, const TrSeq* __restrict__ desc, int cur) {
+    __shared__ uint32_t s_wave[kBlock / 64];
+    __shared__ uint32_t s_off[kBlock + 1];
+    __shared__ int32_t s_row[kBlock];
+    __shared__ long long s_src[kBlock];
+    const int s = seq_of_block<false>(desc, T.n_seq, (int)blockIdx.x);
+    const TrSeq& q = desc[s];
+    const int t = (int)threadIdx.x;
+    const int i = ((int)blockIdx.x - q.blk0) * kBlock + t;
+    const size_t base = (size_t)s * T.M;
+    bool made = false, repeated = false;
+    uint32_t len = 0;
+    long long src0 = 0;
+    int row = -1;
+    if (i < q.n) {
+        const long long E = (long long)q.n_entries;
+        long long o0 = q.offsets_in[i], o1 = q.offsets_in[i + 1];
+        o0 = o0 < 0 ? 0 : (o0 > E ? E : o0);
+        o1 = o1 < 0 ? 0 : (o1 > E ? E : o1);
+        const long long L = o1 > o0 ? o1 - o0 : 0;
+        src0 = o0;
+        row = T.M - 1 - i;
+        if (i == 0) T.top[s] = T.M - q.n;
+        const int32_t id = q.ids[i];
+        const unsigned long long mine = kOccupied | ((unsigned long long)(uint32_t)row << 32) | (uint32_t)id;
+        unsigned long long* tab = T.table + ((size_t)cur * T.n_seq + s) * T.cap;
+        const uint32_t mask = T.cap - 1;
+        uint32_t h = hash_id(id) & mask;
+        int slot = -1, dup_row = -1;
+        for (uint32_t k = 0; k < T.cap; k++) {
+            const unsigned long long old = atomicCAS(&tab[h], 0ull, mine);
+            if (old == 0ull) {
+                slot = (int)h;
+                break;
+            }
+            if ((uint32_t)old == (uint32_t)id) {  // the id occurs twice: the first claim stays
+                repeated = true;
+                dup_row = row;
+                row = (int)((old >> 32) & 0x7fffffffu);
+                break;
+            }
+            h = (h + 1) & mask;
+        }
+        if (slot < 0 && !repeated) {  // (a full table: cannot happen, cap >= 2 * max_tracks)
+            dup_row = row;
+            row = -1;
+        }
+        if (slot >= 0) {
+            len = (uint32_t)(L < (long long)T.H ? L : (long long)T.H);
+            T.head[base + row] = 0;
+            T.len[base + row] = (int32_t)len;
+            made = true;
+        }
+        const size_t ps = ((size_t)cur * T.n_seq + s) * T.M + i;
+        T.row[ps] = row;
+        T.slot[ps] = slot;
+        T.dup_row[ps] = dup_row;
+    }
+    unsigned int* cnt = T.cnt + (size_t)s * 4;
+    wave_count(cnt + 0, made);
+    wave_count(cnt + 2, repeated);
+    uint32_t total;
+    const uint32_t before = block_scan_exclusive(len, s_wave, &total);
+    s_off[t] = before;
+    s_row[t] = row;
+    s_src[t] = src0;
+    if (t == 0) s_off[kBlock] = total;
+    __syncthreads();
+    for (uint32_t e = (uint32_t)t; e < total; e += kBlock) {
+        int lo = 0, hi = kBlock;  // the last track whose prefix is <= e (k_tracks_pack_write)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (s_off[mid] <= e) lo = mid; else hi = mid;
+        }
+        const uint32_t k = e - s_off[lo];  // (k < the track's stored length <= H; src0 + k < n_entries)
+        const float* __restrict__ src = q.fp_in + (size_t)(s_src[lo] + (long long)k) * 3;
+        float* dst = T.hist + ((base + s_row[lo]) * (size_t)T.H + k) * 3;
+        dst[0] = src[0];
+        dst[1] = src[1];
+        dst[2] = src[2];
+    }
+}
+
+// The new tracks of the sequences of a lanes step that have no previous frame: d_last = -1, type_last =
+// MLD_Unspecified - what the depth call answers without a previous cloud (tracklet_depth_module.cpp:93-96).  The depth
+// call saw an all-zero mask for these sequences, so it evaluated none of their previous features and wrote neither array.
+__global__ __launch_bounds__(kBlock) void k_tracks_no_previous(const TrSeq* __restrict__ desc, int n_seq) {
+    const int s = seq_of_block<false>(desc, n_seq, (int)blockIdx.x);
+    const TrSeq& q = desc[s];
+    const int i = ((int)blockIdx.x - q.blk0) * kBlock + (int)threadIdx.x;
+    if (i >= q.n || !q.is_new[i]) return;
+    q.d_last_w[i] = -1.0f;
+    if (q.len_out) q.len_out[i] = (int32_t)MLD_Unspecified;
+}
+
 char g_create_error[512] = "";
 
 }  // namespace
@@ -442,6 +577,7 @@ struct mld_tracks : mld_batch::Object {
     TrDev d{};
     std::vector<void*> allocs;
     uint8_t* own_mask = nullptr;  // [n_seq][M]: the masks of a begin without is_new_out
+    uint8_t* zero_mask = nullptr; // [M] zeros: the mask the depth call gets for a sequence without a previous frame
     mld_batch::DescRing<TrSeq> ring;
     // host-side frame state: everything a call needs is known when it is issued, nothing is read back
     int committed = 0;      // the table / per-track arrays of the last committed frame
@@ -451,6 +587,7 @@ struct mld_tracks : mld_batch::Object {
     std::vector<const int32_t*> ids_pending;
     std::vector<uint8_t*> mask_pending;
     std::vector<const uint8_t*> mask_table;  // mld_tracklets_step_device
+    std::vector<uint8_t> lane_last;          // mld_tracklets_step_lanes_device: have_last of the lanes that do not restart
 };
 
 namespace {
@@ -468,6 +605,21 @@ int layout_blocks(mld_tracks* tr, int per_track, int64_t* total, int64_t* total_
     }
     *total = b;
     *total_prev = bp;
+    return MLD_OK;
+}
+
+// What mld_tracks_begin_device refuses, without a change of state.
+int check_begin(mld_tracks* tr, const char* fn, const int32_t* const* ids, const int64_t* n_tracks, uint8_t* const* is_new_out) {
+    auto refuse = [&](int code, const char* what) {
+        tr->err = std::string(fn) + ": " + what;
+        return code;
+    };
+    if (!ids || !n_tracks) return refuse(MLD_ERR_INVALID_ARG, "null table");
+    for (int s = 0; s < tr->d.n_seq; s++) {
+        if (n_tracks[s] < 0) return refuse(MLD_ERR_INVALID_ARG, "negative track count");
+        if (n_tracks[s] > tr->d.M) return refuse(MLD_ERR_CAPACITY, "more tracks than max_tracks");
+        if (n_tracks[s] > 0 && (!ids[s] || (is_new_out && !is_new_out[s]))) return refuse(MLD_ERR_INVALID_ARG, "null array");
+    }
     return MLD_OK;
 }
 
@@ -503,6 +655,7 @@ int allocate(mld_tracks* tr) {
     if ((rc = dev_alloc(tr, &d.pack_base, pack_blocks, false))) return rc;
     if ((rc = dev_alloc(tr, &d.pack_meta, S * M, false))) return rc;
     if ((rc = dev_alloc(tr, &tr->own_mask, S * M, true))) return rc;
+    if ((rc = dev_alloc(tr, &tr->zero_mask, M, true))) return rc;
     if ((rc = tr->ring.allocate(tr, d.n_seq))) return rc;
     // (the table starts as zeros, like the rest of the store's memory)
     MLD_HIP(tr, hipMemsetAsync(tr->ring.d_desc, 0, tr->ring.gen_bytes, tr->stream));
@@ -541,6 +694,7 @@ mld_tracks* mld_tracks_create(mld_ctx* ctx, int n_seq, int64_t max_tracks, int m
         tr->ids_pending.assign((size_t)n_seq, nullptr);
         tr->mask_pending.assign((size_t)n_seq, nullptr);
         tr->mask_table.assign((size_t)n_seq, nullptr);
+        tr->lane_last.assign((size_t)n_seq, 0);
         return allocate(tr);
     };
     return mld_batch::create_object<mld_tracks>(g_create_error, "mld_tracks_create", refusal(), ctx, status_out, init, free_own);
@@ -552,14 +706,9 @@ const char* mld_tracks_last_error(const mld_tracks* tr) { return tr ? tr->err.c_
 
 int mld_tracks_begin_device(mld_tracks* tr, const int32_t* const* ids, const int64_t* n_tracks, uint8_t* const* is_new_out) {
     if (!tr) return MLD_ERR_INVALID_ARG;
-    if (!ids || !n_tracks) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_begin_device: null table");
+    int rc = check_begin(tr, "mld_tracks_begin_device", ids, n_tracks, is_new_out);
+    if (rc) return rc;
     const int S = tr->d.n_seq;
-    for (int s = 0; s < S; s++) {
-        if (n_tracks[s] < 0) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_begin_device: negative track count");
-        if (n_tracks[s] > tr->d.M) return fail(tr, MLD_ERR_CAPACITY, "mld_tracks_begin_device: more tracks than max_tracks");
-        if (n_tracks[s] > 0 && (!ids[s] || (is_new_out && !is_new_out[s])))
-            return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_begin_device: null array");
-    }
     MLD_HIP(tr, hipSetDevice(tr->device));
     for (int s = 0; s < S; s++) {
         TrSeq& q = tr->ring.stage[(size_t)s];
@@ -576,8 +725,7 @@ int mld_tracks_begin_device(mld_tracks* tr, const int32_t* const* ids, const int
     tr->epoch++;
     tr->begun = true;
     int64_t blocks = 0, blocks_prev = 0;
-    int rc = layout_blocks(tr, 1, &blocks, &blocks_prev);
-    if (rc) return rc;
+    if ((rc = layout_blocks(tr, 1, &blocks, &blocks_prev))) return rc;
     if (blocks == 0) return MLD_OK;
     if ((rc = tr->ring.upload(tr))) return rc;
     hipLaunchKernelGGL(k_tracks_lookup, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed,
@@ -690,6 +838,88 @@ int mld_tracks_export_packed_device(mld_tracks* tr, float* const* fp_out, const 
     return MLD_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The selected sequences emptied and, with tables, loaded: mld_tracks_import_packed_device, mld_tracks_reset_device
+// (ids == nullptr: no tracks anywhere) and the restart of mld_tracklets_step_lanes_device.  Everything is checked before
+// anything is queued or any host state changes.
+int import_packed(mld_tracks* tr, const char* fn, const uint8_t* select, const int32_t* const* ids, const int64_t* n_tracks,
+                  const int64_t* const* offsets, const float* const* fp, const int64_t* n_entries) {
+    auto refuse = [&](int code, const char* what) {
+        tr->err = std::string(fn) + ": " + what;
+        return code;
+    };
+    const int S = tr->d.n_seq;
+    const bool load = ids != nullptr;
+    if (load && (!n_tracks || !offsets || !fp || !n_entries)) return refuse(MLD_ERR_INVALID_ARG, "null table");
+    const int64_t reset_blocks = ((int64_t)tr->d.cap + kBlock - 1) / kBlock;
+    int64_t blocks = 0, blocks_reset = 0;
+    for (int s = 0; s < S; s++) {
+        if (select && !select[s]) continue;
+        blocks_reset += reset_blocks;
+        if (!load) continue;
+        if (n_tracks[s] < 0) return refuse(MLD_ERR_INVALID_ARG, "negative track count");
+        if (n_entries[s] < 0) return refuse(MLD_ERR_INVALID_ARG, "negative n_entries");
+        if (n_tracks[s] > tr->d.M) return refuse(MLD_ERR_CAPACITY, "more tracks than max_tracks");
+        // (without entries nothing of fp[s] is read: every track is stored with length 0)
+        if (n_tracks[s] > 0 && (!ids[s] || !offsets[s] || (!fp[s] && n_entries[s] > 0)))
+            return refuse(MLD_ERR_INVALID_ARG, "null array");
+        blocks += (n_tracks[s] + kBlock - 1) / kBlock;
+    }
+    if (blocks > 0x7fffffff || blocks_reset > 0x7fffffff) return refuse(MLD_ERR_CAPACITY, "more than 2^31 blocks in one launch");
+    MLD_HIP(tr, hipSetDevice(tr->device));
+    int64_t b = 0, br = 0;
+    for (int s = 0; s < S; s++) {
+        TrSeq& q = tr->ring.stage[(size_t)s];
+        q = TrSeq{};
+        q.blk0 = (int32_t)b;
+        q.blk0_prev = (int32_t)br;
+        if (select && !select[s]) continue;  // (no block of either launch: the sequence is not touched)
+        br += reset_blocks;
+        if (load && n_tracks[s] > 0) {
+            q.ids = ids[s];
+            q.offsets_in = offsets[s];
+            q.fp_in = fp[s];
+            q.n_entries = n_entries[s];
+            q.n = (int32_t)n_tracks[s];
+            b += ((int64_t)q.n + kBlock - 1) / kBlock;
+        }
+    }
+    if (blocks_reset > 0) {
+        int rc = tr->ring.upload(tr);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_tracks_reset, dim3((unsigned)blocks_reset), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed);
+        MLD_HIP(tr, hipGetLastError());
+        if (blocks > 0) {
+            hipLaunchKernelGGL(k_tracks_import, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed);
+            MLD_HIP(tr, hipGetLastError());
+        }
+    }
+    // the host's view follows what was queued (as in mld_tracks_commit_device)
+    for (int s = 0; s < S; s++)
+        if (!select || select[s]) tr->n_committed[(size_t)s] = tr->ring.stage[(size_t)s].n;
+    tr->begun = false;  // a begun frame is abandoned: its look-up saw what the import replaces
+    return MLD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mld_tracks_import_packed_device(mld_tracks* tr, const uint8_t* select, const int32_t* const* ids, const int64_t* n_tracks,
+                                    const int64_t* const* offsets, const float* const* fp, const int64_t* n_entries) {
+    if (!tr) return MLD_ERR_INVALID_ARG;
+    if (!ids) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_import_packed_device: null table");
+    return import_packed(tr, "mld_tracks_import_packed_device", select, ids, n_tracks, offsets, fp, n_entries);
+}
+
+int mld_tracks_reset_device(mld_tracks* tr, const uint8_t* select) {
+    if (!tr) return MLD_ERR_INVALID_ARG;
+    return import_packed(tr, "mld_tracks_reset_device", select, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
 int mld_tracks_counts(mld_tracks* tr, int64_t* counts_out) {
     if (!tr) return MLD_ERR_INVALID_ARG;
     if (!counts_out) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracks_counts: null output");
@@ -726,23 +956,114 @@ int mld_tracks_counts(mld_tracks* tr, int64_t* counts_out) {
     return MLD_OK;
 }
 
-int mld_tracklets_step_device(mld_ctx* ctx, mld_tracks* tr, int bank_cur, int have_last, const int32_t* const* ids,
-                              const float* const* u_new, const float* const* v_new, const float* const* u_old,
-                              const float* const* v_old, const int64_t* n_tracks, float* const* d_cur_out,
-                              float* const* d_last_out, int32_t* const* type_cur_out, int32_t* const* type_last_out) {
-    if (!tr) return MLD_ERR_INVALID_ARG;
-    if (!ctx || ctx != tr->ctx) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracklets_step_device: the store belongs to another context");
-    if (!d_cur_out || !d_last_out) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracklets_step_device: null output table");
-    int rc = mld_tracks_begin_device(tr, ids, n_tracks, nullptr);
+// mld_tracklets_depths_device with have_last per sequence, on that call alone (the depth path is not touched).  Equal
+// flags: that call.  Mixed flags: the sequences with a previous frame and those without go through it one group after the
+// other, each call with the other group's track counts at zero - a sequence without tracks has no feature on either of
+// its slots, so nothing of its previous-bank slot is read, and the group without a previous frame is answered -1 /
+// MLD_Unspecified.  The call with have_last = 1 checks the previous-bank slot of EVERY sequence as it always does
+// (include/mld.h states it).  (The step below needs one launch set only: it owns the masks.)
+int mld_tracklets_depths_lanes_device(mld_ctx* ctx, int n_seq, int bank_cur, const uint8_t* have_last, const float* const* u_new,
+                                      const float* const* v_new, const float* const* u_old, const float* const* v_old,
+                                      const uint8_t* const* is_new, const int64_t* n_tracks, float* const* d_cur_out,
+                                      float* const* d_last_out, int32_t* const* type_cur_out, int32_t* const* type_last_out) {
+    if (!ctx || !have_last || n_seq < 1) return MLD_ERR_INVALID_ARG;
+    int with = 0;
+    for (int q = 0; q < n_seq; q++) with += have_last[q] != 0;
+    if (with == 0 || with == n_seq || !n_tracks)  // (a null table: the call's own refusal)
+        return mld_tracklets_depths_device(ctx, n_seq, bank_cur, with ? 1 : 0, u_new, v_new, u_old, v_old, is_new, n_tracks,
+                                           d_cur_out, d_last_out, type_cur_out, type_last_out);
+    std::vector<int64_t> n_with((size_t)n_seq), n_without((size_t)n_seq);
+    for (int q = 0; q < n_seq; q++) {
+        n_with[(size_t)q] = have_last[q] ? n_tracks[q] : 0;
+        n_without[(size_t)q] = have_last[q] ? 0 : n_tracks[q];
+    }
+    const int rc = mld_tracklets_depths_device(ctx, n_seq, bank_cur, 1, u_new, v_new, u_old, v_old, is_new, n_with.data(),
+                                               d_cur_out, d_last_out, type_cur_out, type_last_out);
     if (rc) return rc;
-    for (int s = 0; s < tr->d.n_seq; s++) tr->mask_table[(size_t)s] = tr->mask_pending[(size_t)s];
-    rc = mld_tracklets_depths_device(ctx, tr->d.n_seq, bank_cur, have_last, u_new, v_new, u_old, v_old, tr->mask_table.data(),
+    return mld_tracklets_depths_device(ctx, n_seq, bank_cur, 0, u_new, v_new, u_old, v_old, is_new, n_without.data(), d_cur_out,
+                                       d_last_out, type_cur_out, type_last_out);
+}
+
+// have_last == nullptr: the scalar call (`uniform` for every sequence, no restart).
+static int tracklets_step(const char* fn, mld_ctx* ctx, mld_tracks* tr, int bank_cur, int uniform, const uint8_t* have_last,
+                          const uint8_t* restart, const int32_t* const* ids, const float* const* u_new,
+                          const float* const* v_new, const float* const* u_old, const float* const* v_old,
+                          const int64_t* n_tracks, float* const* d_cur_out, float* const* d_last_out,
+                          int32_t* const* type_cur_out, int32_t* const* type_last_out) {
+    auto refuse = [&](const char* what) {
+        tr->err = std::string(fn) + ": " + what;
+        return MLD_ERR_INVALID_ARG;
+    };
+    if (!ctx || ctx != tr->ctx) return refuse("the store belongs to another context");
+    if (!d_cur_out || !d_last_out) return refuse("null output table");
+    const int S = tr->d.n_seq;
+    int rc;
+    bool any_restart = false;
+    for (int s = 0; restart && s < S; s++) any_restart = any_restart || restart[s] != 0;
+    if (any_restart) {  // (what the begin would refuse is refused before a lane is emptied)
+        if ((rc = check_begin(tr, fn, ids, n_tracks, nullptr))) return rc;
+        if ((rc = import_packed(tr, fn, restart, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
+    }
+    if ((rc = mld_tracks_begin_device(tr, ids, n_tracks, nullptr))) return rc;
+    for (int s = 0; s < S; s++) tr->mask_table[(size_t)s] = tr->mask_pending[(size_t)s];
+    int with = 0;
+    for (int s = 0; have_last && s < S; s++) {
+        tr->lane_last[(size_t)s] = have_last[s] && !(restart && restart[s]) ? 1 : 0;
+        with += tr->lane_last[(size_t)s];
+    }
+    const bool mixed = have_last && with > 0 && with < S;
+    if (have_last && !mixed) uniform = with > 0;
+    // Mixed flags, ONE launch set: the depth call runs with have_last = 1 and sees an all-zero mask for a sequence
+    // without a previous frame - no previous feature of it is evaluated, nothing of its previous-bank slot is read and
+    // its d_last is not written; k_tracks_no_previous then answers its new tracks as the call without a cloud would.
+    if (mixed)
+        for (int s = 0; s < S; s++)
+            if (!tr->lane_last[(size_t)s]) tr->mask_table[(size_t)s] = tr->zero_mask;
+    rc = mld_tracklets_depths_device(ctx, S, bank_cur, mixed ? 1 : uniform, u_new, v_new, u_old, v_old, tr->mask_table.data(),
                                      n_tracks, d_cur_out, d_last_out, type_cur_out, type_last_out);
     if (rc) {  // (the frame stays begun and uncommitted: the next begin replaces it)
         tr->err = std::string("mld_tracklets_depths_device: ") + mld_last_error(ctx);
         return rc;
     }
+    if (mixed) {
+        for (int s = 0; s < S; s++) {
+            TrSeq& q = tr->ring.stage[(size_t)s];
+            q = TrSeq{};
+            if (tr->lane_last[(size_t)s]) continue;  // (no block: layout_blocks gives blocks to n > 0 only)
+            q.is_new = tr->mask_pending[(size_t)s];
+            q.d_last_w = d_last_out[s];
+            q.len_out = type_last_out ? type_last_out[s] : nullptr;
+            q.n = tr->n_pending[(size_t)s];
+        }
+        int64_t blocks = 0, blocks_prev = 0;
+        if ((rc = layout_blocks(tr, 1, &blocks, &blocks_prev))) return rc;
+        if (blocks > 0) {
+            if ((rc = tr->ring.upload(tr))) return rc;
+            hipLaunchKernelGGL(k_tracks_no_previous, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->ring.d_desc, S);
+            MLD_HIP(tr, hipGetLastError());
+        }
+    }
     return mld_tracks_commit_device(tr, u_new, v_new, u_old, v_old, d_cur_out, d_last_out);
+}
+
+int mld_tracklets_step_device(mld_ctx* ctx, mld_tracks* tr, int bank_cur, int have_last, const int32_t* const* ids,
+                              const float* const* u_new, const float* const* v_new, const float* const* u_old,
+                              const float* const* v_old, const int64_t* n_tracks, float* const* d_cur_out,
+                              float* const* d_last_out, int32_t* const* type_cur_out, int32_t* const* type_last_out) {
+    if (!tr) return MLD_ERR_INVALID_ARG;
+    return tracklets_step("mld_tracklets_step_device", ctx, tr, bank_cur, have_last, nullptr, nullptr, ids, u_new, v_new, u_old,
+                          v_old, n_tracks, d_cur_out, d_last_out, type_cur_out, type_last_out);
+}
+
+int mld_tracklets_step_lanes_device(mld_ctx* ctx, mld_tracks* tr, int bank_cur, const uint8_t* have_last, const uint8_t* restart,
+                                    const int32_t* const* ids, const float* const* u_new, const float* const* v_new,
+                                    const float* const* u_old, const float* const* v_old, const int64_t* n_tracks,
+                                    float* const* d_cur_out, float* const* d_last_out, int32_t* const* type_cur_out,
+                                    int32_t* const* type_last_out) {
+    if (!tr) return MLD_ERR_INVALID_ARG;
+    if (!have_last) return fail(tr, MLD_ERR_INVALID_ARG, "mld_tracklets_step_lanes_device: null have_last");
+    return tracklets_step("mld_tracklets_step_lanes_device", ctx, tr, bank_cur, 0, have_last, restart, ids, u_new, v_new, u_old,
+                          v_old, n_tracks, d_cur_out, d_last_out, type_cur_out, type_last_out);
 }
 
 }  // extern "C"

@@ -9,8 +9,10 @@ to integer pixels), both CalculateDepth calls and the float32 scatter — one C-
 The previous frame is NOT re-projected as the reference does (:115 -> setInputCloud): its frame slot (cloud, pixel
 map, ground plane) is kept and the two slots ping-pong.  The tracklet map itself (ids seen so far, per-track
 history) is host bookkeeping in the one-frame TrackletDepthModule, kept here in Python; at batch size it lives on the
-GPU: TrackletStore (mld_tracks_*) decides the new tracks, keeps the histories, drops the dead tracks and exports the
-stored tracks in message order, and TrackletBatch.step runs a whole frame of every sequence with it.  SemanticLabels
+GPU: TrackletStore (mld_tracks_*) decides the new tracks, keeps the histories, drops the dead tracks, exports the
+stored tracks in message order and takes a packed export back in (import_packed: a store continues in another store,
+on another context or GPU), and TrackletBatch.step runs a whole frame of every sequence with it - the sequences being
+lanes that start, restart (restart=...) and resume (set_previous) independently.  SemanticLabels
 (mld_labels_*) is the node that follows tracklets_depth in the reference's launch files: the label of every track by
 majority vote in a window of a label image (matches_conversion_ros_tool, semantic_labels.cpp:50-72).  SemanticPlanes
 (mld_semantic_planes_*) is the ground plane process() builds from the label image of every frame (:269-284), for all
@@ -284,6 +286,46 @@ class TrackletStore(_BatchObject):
         self._check(self._lib.mld_tracks_export_packed_device(self._tr, self._vp(fp_out), cap, self._vp(offsets_out)))
         self._hold((list(fp_out) if fp_out is not None else None, list(offsets_out) if offsets_out is not None else None),
                    "export_packed")
+
+    def _select(self, select):
+        if select is None:
+            return None
+        if len(select) != self.S:
+            raise ValueError(f"select: expected {self.S} flags, one per sequence")
+        return (C.c_uint8 * self.S)(*[1 if x else 0 for x in select])
+
+    def import_packed(self, ids, offsets, fp, select=None):
+        """The inverse of export_packed() (mld_tracks_import_packed_device): the committed frame of every selected
+        sequence is replaced by the given tracks, as if a fresh store had been brought to that state.  ids: S int32 CUDA
+        tensors [n]; offsets: S int64 CUDA tensors [n + 1]; fp: S contiguous float32 CUDA tensors [entries, 3] - what
+        export_packed() of a store (of any max_tracks / max_history, on any context) wrote, with the ids of that frame.
+        select: None (all), or S flags; the entries of a sequence that is not selected may be None and the sequence is
+        not touched.  A selected sequence whose ids is None or empty is emptied.  Histories longer than max_history keep
+        their newest entries; offsets are clamped to the entries fp holds.  A begun frame is abandoned."""
+        S = self.S
+        for name, ts in (("ids", ids), ("offsets", offsets), ("fp", fp)):
+            if len(ts) != S:
+                raise ValueError(f"{name}: expected {S} entries, one per sequence")
+        nt, ne = [], []
+        for s in range(S):
+            on = select is None or bool(select[s])
+            n = int(ids[s].shape[0]) if on and ids[s] is not None else 0
+            if n:
+                if offsets[s] is None or int(offsets[s].numel()) != n + 1 or offsets[s].element_size() != 8 or not offsets[s].is_contiguous():
+                    raise ValueError(f"sequence {s}: offsets must be a contiguous int64 tensor of {n + 1} entries")
+                if fp[s] is not None and (fp[s].element_size() != 4 or not fp[s].is_contiguous()):
+                    raise ValueError(f"sequence {s}: fp must be a contiguous float32 tensor")
+            nt.append(n)
+            ne.append(int(fp[s].numel()) // 3 if n and fp[s] is not None else 0)
+        live = lambda ts: [t if nt[s] else None for s, t in enumerate(ts)]  # noqa: E731
+        self._check(self._lib.mld_tracks_import_packed_device(self._tr, self._select(select), self._ptrs(live(ids)),
+                                                              (C.c_int64 * S)(*nt), self._ptrs(live(offsets)),
+                                                              self._ptrs(live(fp)), (C.c_int64 * S)(*ne)))
+        self._hold((live(ids), live(offsets), live(fp)), "import_packed")
+
+    def reset(self, select=None):
+        """Empties the selected sequences (None: all) - import_packed() of no tracks (mld_tracks_reset_device)."""
+        self._check(self._lib.mld_tracks_reset_device(self._tr, self._select(select)))
 
     def counts(self) -> np.ndarray:
         """[S, 6] int64 of the last committed frame, columns COUNT_NAMES.  Synchronises."""
@@ -794,7 +836,12 @@ class TrackletBatch:
     mld_tracklets_depths_device): the estimator's frame slots are two banks of S slots, sequence s keeps its current
     frame in slot bank * S + s and its previous frame, still resident, in the other bank.  Device tensors in, device
     tensors out; asynchronous.  run() takes the new-track masks from the caller, who then keeps the tracklet maps
-    (as TrackletDepthModule does); step() takes the track ids and keeps the maps on the GPU in a TrackletStore."""
+    (as TrackletDepthModule does); step() takes the track ids and keeps the maps on the GPU in a TrackletStore.
+
+    The sequences are LANES that start, restart and resume independently: `lane_has_last[s]` says whether the previous
+    bank holds a previous frame of lane s (every lane has one after a step; set_previous() gives one to a resumed lane),
+    and step(restart=...) / run(restart=...) start a new recording in a lane - the construction of a new
+    TrackletDepthModule.  `have_last` is true when every lane has a previous frame; assigning it sets every lane."""
 
     def __init__(self, parameters, camera: CameraPinhole, transform_lidar_to_cam, n_seq: int, max_tracks: int,
                  device: int = 0, list_capacity=None):
@@ -805,8 +852,10 @@ class TrackletBatch:
         if list_capacity:
             self.est.setListCapacity(*list_capacity)
         self.bank = 0
-        self.have_last = False
+        self.lane_has_last = [False] * self.S
         self._keep = None
+        self._keep_previous = ([], [])  # tensors of set_previous(): held like `_keep`, until their slot is overwritten
+        self._slot_set = [[False] * self.S, [False] * self.S]  # per bank and lane: has the slot ever held a cloud?
         self.max_tracks = int(max_tracks)
         self.store: Optional[TrackletStore] = None
         self.semantic_labels: Optional[SemanticLabels] = None
@@ -816,6 +865,66 @@ class TrackletBatch:
         self.depth_reports: Optional[DepthReports] = None
         self.inliers: Optional[PlaneInliers] = None
         self.feature_traces: Optional[FeatureTraces] = None
+
+    @property
+    def have_last(self) -> bool:
+        return all(self.lane_has_last)
+
+    @have_last.setter
+    def have_last(self, value):
+        self.lane_has_last = [bool(value)] * self.S
+
+    def _lane_flags(self, restart):
+        """(uniform have_last or None, have_last flags, restart flags or None) of the next step() / run()."""
+        S = self.S
+        if restart is not None and len(restart) != S:
+            raise ValueError(f"restart: expected {S} flags, one per lane")
+        again = [bool(x) for x in restart] if restart is not None else [False] * S
+        last = [h and not r for h, r in zip(self.lane_has_last, again)]
+        if not any(again) and all(x == last[0] for x in last):
+            return last[0], None, None
+        return None, (C.c_uint8 * S)(*last), (C.c_uint8 * S)(*again) if any(again) else None
+
+    def _project(self, f, last):
+        """setInputCloud of the current bank from the tables `f`.  A call with mixed flags checks the previous-bank slot
+        of every lane though it reads nothing of a lane without a previous frame (include/mld.h); where such a slot
+        never held a cloud - a batch's first step only - it takes the lane's current cloud and plane, which satisfies
+        the check and is never read."""
+        S, est, lib = self.S, self.est, self.est._lib
+        co = f["coeffs"].ctypes.data_as(C.POINTER(C.c_float))
+        est._check(lib.mld_set_clouds_planes_range_device(est._ctx, self.bank * S, S, f["clouds"], f["n"], 16, co, f["masks"]))
+        self._slot_set[self.bank] = [True] * S
+        for q in range(S if last is not None else 0):
+            if not last[q] and not self._slot_set[1 - self.bank][q]:
+                est._check(lib.mld_set_clouds_planes_range_device(
+                    est._ctx, (1 - self.bank) * S + q, 1, (C.c_void_p * 1)(f["clouds"][q]), (C.c_int64 * 1)(f["n"][q]), 16,
+                    f["coeffs"][q].ctypes.data_as(C.POINTER(C.c_float)), (C.c_void_p * 1)(f["masks"][q])))
+                self._slot_set[1 - self.bank][q] = True
+
+    def _stepped(self, f):
+        """The arrays must outlive the asynchronous launches; the previous frame's clouds stay referenced by their slots."""
+        self._keep = (self._keep[1] if self._keep else None, f)
+        self._keep_previous = (self._keep_previous[1], [])
+        self.bank = 1 - self.bank
+        self.have_last = True
+
+    def set_previous(self, lane: int, cloud, coeffs, mask):
+        """Gives lane `lane` a previous frame without a step - for a lane whose store was loaded with
+        store.import_packed(): setInputCloud(cloud, plane) on the ONE slot (1 - bank) * S + lane
+        (mld_set_clouds_planes_range_device), and the lane counts as having a previous frame.  cloud: a float32 CUDA
+        tensor [n, 4]; coeffs: 4 floats (host); mask: the int32 inlier bitmask."""
+        S, est, lib = self.S, self.est, self.est._lib
+        if not 0 <= int(lane) < S:
+            raise ValueError(f"lane must be in 0 .. {S - 1}")
+        co = np.ascontiguousarray(coeffs, dtype=np.float32).reshape(4)
+        est._after_torch(cloud)
+        est._check(lib.mld_set_clouds_planes_range_device(est._ctx, (1 - self.bank) * S + int(lane), 1,
+                                                          (C.c_void_p * 1)(int(cloud.data_ptr())), (C.c_int64 * 1)(int(cloud.shape[0])),
+                                                          16, co.ctypes.data_as(C.POINTER(C.c_float)),
+                                                          (C.c_void_p * 1)(int(mask.data_ptr()))))
+        self._keep_previous[1].append((cloud, mask))
+        self._slot_set[1 - self.bank][int(lane)] = True
+        self.lane_has_last[int(lane)] = True
 
     def attach_planes(self, max_points: int = 1 << 19) -> SemanticPlanes:
         """The semantic ground plane estimator of the S sequences that semantic_planes() runs ahead of a step, for clouds
@@ -1050,26 +1159,29 @@ class TrackletBatch:
                 "features": (list(u_new), list(v_new)),
                 "current": (list(d_cur), list(t_cur) if t_cur is not None else None)}
 
-    def step(self, f, nxt: Optional["TrackletBatch"] = None, handover: str = "projection"):
+    def step(self, f, nxt: Optional["TrackletBatch"] = None, handover: str = "projection", restart=None):
         """run() with the tracklet maps on the GPU (mld_tracklets_step_device): projection of the current bank, then
         new-track decision -> depths -> histories as one asynchronous chain.  `f` from prepare_step(); attach_store()
-        first.  The histories are read with store.export(...)."""
+        first.  The histories are read with store.export(...).  restart: None, or S flags - a lane with a flag starts a
+        new recording on this frame: its store is emptied first, every id of it is new and its d_last is -1.  With lanes
+        that differ (restart, or lane_has_last) the call is mld_tracklets_step_lanes_device, else today's."""
         if self.store is None:
             raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.step without attach_store")
         S, est, lib = self.S, self.est, self.est._lib
-        est._check(lib.mld_set_clouds_planes_range_device(est._ctx, self.bank * S, S, f["clouds"], f["n"], 16,
-                                                          f["coeffs"].ctypes.data_as(C.POINTER(C.c_float)), f["masks"]))
+        uniform, last, again = self._lane_flags(restart)
+        self._project(f, last)
         if nxt is not None and nxt is not self:
             if handover == "classify":
                 nxt.est.orderAfterClassify(est)
             else:
                 nxt.est.orderAfter(est)
-        self.store._check(lib.mld_tracklets_step_device(est._ctx, self.store._tr, self.bank, 1 if self.have_last else 0,
-                                                        f["ids"], f["u_new"], f["v_new"], f["u_old"], f["v_old"], f["nt"],
-                                                        f["d_cur"], f["d_last"], f["t_cur"], f["t_last"]))
-        self._keep = (self._keep[1] if self._keep else None, f)
-        self.bank = 1 - self.bank
-        self.have_last = True
+        tail = (f["ids"], f["u_new"], f["v_new"], f["u_old"], f["v_old"], f["nt"], f["d_cur"], f["d_last"], f["t_cur"], f["t_last"])
+        if last is None:
+            rc = lib.mld_tracklets_step_device(est._ctx, self.store._tr, self.bank, 1 if uniform else 0, *tail)
+        else:
+            rc = lib.mld_tracklets_step_lanes_device(est._ctx, self.store._tr, self.bank, last, again, *tail)
+        self.store._check(rc)
+        self._stepped(f)
 
     def prepare(self, clouds, coeffs, masks, u_new, v_new, u_old, v_old, is_new, d_cur, d_last, t_cur=None, t_last=None):
         """Pointer tables of one frame of every sequence (reusable: a steady-state caller prepares one per bank).
@@ -1089,26 +1201,27 @@ class TrackletBatch:
                 "features": (list(u_new), list(v_new)),
                 "current": (list(d_cur), list(t_cur) if t_cur is not None else None)}
 
-    def run(self, f, nxt: Optional["TrackletBatch"] = None, handover: str = "projection"):
+    def run(self, f, nxt: Optional["TrackletBatch"] = None, handover: str = "projection", restart=None):
         """One frame of every sequence from prepared tables: projection of the current bank, then the tracklet call.
         `nxt`: another TrackletBatch (other sequences) that takes the next step - it is released as soon as this
-        projection has finished, so that its projection runs beside these feature kernels (include/mld.h "Two contexts")."""
+        projection has finished, so that its projection runs beside these feature kernels (include/mld.h "Two contexts").
+        restart: None, or S flags - a lane with a flag starts a new recording on this frame (the caller's mask marks
+        all its tracks new): its previous frame is not used and its d_last is -1."""
         S, est, lib = self.S, self.est, self.est._lib
-        est._check(lib.mld_set_clouds_planes_range_device(est._ctx, self.bank * S, S, f["clouds"], f["n"], 16,
-                                                          f["coeffs"].ctypes.data_as(C.POINTER(C.c_float)), f["masks"]))
+        uniform, last, _ = self._lane_flags(restart)
+        self._project(f, last)
         if nxt is not None and nxt is not self:
             # (released at the end of this projection, or behind this step's classification kernel: include/mld.h)
             if handover == "classify":
                 nxt.est.orderAfterClassify(est)
             else:
                 nxt.est.orderAfter(est)
-        est._check(lib.mld_tracklets_depths_device(est._ctx, S, self.bank, 1 if self.have_last else 0, f["u_new"], f["v_new"],
-                                                   f["u_old"], f["v_old"], f["is_new"], f["nt"], f["d_cur"], f["d_last"],
-                                                   f["t_cur"], f["t_last"]))
-        # the arrays must outlive the asynchronous launches; the previous frame's clouds stay referenced by their slots
-        self._keep = (self._keep[1] if self._keep else None, f)
-        self.bank = 1 - self.bank
-        self.have_last = True
+        tail = (f["u_new"], f["v_new"], f["u_old"], f["v_old"], f["is_new"], f["nt"], f["d_cur"], f["d_last"], f["t_cur"], f["t_last"])
+        if last is None:
+            est._check(lib.mld_tracklets_depths_device(est._ctx, S, self.bank, 1 if uniform else 0, *tail))
+        else:
+            est._check(lib.mld_tracklets_depths_lanes_device(est._ctx, S, self.bank, last, *tail))
+        self._stepped(f)
 
     def frame(self, clouds, *args, **kw):
         self.est._after_torch(clouds[0])
