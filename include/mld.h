@@ -1175,6 +1175,110 @@ int mld_feature_traces_collect_tracks_device(mld_feature_traces* ft, const float
                                              int32_t* const* road_out, int32_t* const* road_inl_out);
 
 /*
+ * Coverage maps of a batch — where in the image a feature can get a depth, for n_seq independent sequences in one call.
+ * Whether a feature at pixel (x, y) clears the neighbour test, and whether the road fallback can run for it, is decided
+ * before any floating-point fit: it depends only on the pixel map, the inlier mask and the window rule of
+ * NeighborFinderPixel::getNeighbors (NeighborFinderPixel.cpp:60-95, with DepthEstimator.cpp:680-681 and :782-830).  This
+ * object evaluates that neighbour stage at EVERY integer pixel of every sequence, in GPU memory, and names the best pixel
+ * per bucket of the image - the list a feature detector would use.  Exact integers throughout; no tolerance path.
+ *
+ * The pixel (x, y), 0 <= x < W, 0 <= y < H, stands for the feature ((double)x, (double)y), the coordinate the tracklet
+ * layer passes.  The windows are those of mld_feature_traces stage 1 and stage 4: half sizes
+ *   halfX = (double)pixelarea_search_witdh * 0.5 * (double)sx,  halfY = (double)pixelarea_search_height * 0.5 * (double)sy
+ * with (sx, sy) = (1.0f, 1.0f) for the narrow and (2.0f, 1.5f) for the wide window, the edges clamped in f64 to [0, W - 1]
+ * and [0, H - 1], the bounds truncated with (int), both bounds scanned inclusive.  Column bounds depend on x only and row
+ * bounds on y only; both are evaluated by that rule and never as x +- const (the clamped borders and the truncation of a
+ * non-integer half size - C0 wide: 6.75 - differ).
+ *
+ * Per-cell properties, from map[s], index[s], cam[s], coeffs and mask_dev[s] (the arrays
+ * mld_feature_traces_collect_device takes):
+ *   occupied  the map value is not -1
+ *   inlier    occupied, and the mask bit of index[r] is set
+ *   far       occupied, and the f32 un-normalised point-to-plane distance of T_lidar_cam * p_cam (f64 transform, then cast
+ *             to f32) exceeds ransac_plane_point_distance_treshold: operation for operation MLD_TRACE_ROAD_FAR_NEIGHBOUR
+ *   A map value other than -1 outside [0, index_len[s]) and an index value outside [0, n_points[s]) make the cell EMPTY and
+ *   set MLD_COVERAGE_FLAG_BAD_INPUT in the sequence's record; no read leaves the arrays as the host tables size them.
+ *   A sequence without a plane - mask_dev[s] NULL, or coeffs NULL, or do_use_ransac_plane off - has no inlier and no far
+ *   cells, and bit 1 of reach is 0 everywhere.
+ *
+ * Per-pixel outputs, W * H uint8 each with index x + y * W; every table and every entry is optional; counts saturate at 255:
+ *   nb_out        occupied cells of the narrow window: n_nb of mld_feature_trace
+ *   road_out, road_inl_out, road_far_out   occupied, inlier and far cells of the wide window
+ *   reach_out     bit 0: n_nb >= radiusSearch_count_min (compared as unsigned): a feature there is not type 2
+ *                 bit 1: bit 0, the sequence has a plane, n_road >= radiusSearch_count_min, n_far == 0 and n_inl >= 3: the
+ *                        road estimator can run if the main path does not succeed
+ *                 with set_all_depths_to_zero both bits are 0
+ * record_out_dev: n_seq records (DEVICE memory, 8-byte aligned), every one written completely on every call.
+ * Bucket proposals (bucket_out non-NULL): the image is cut into ceil(W / bucket_w) x ceil(H / bucket_h) buckets in
+ *   row-major order; bucket b gets the int32[3] entry (x, y, n_nb) at bucket_out[s] + 3 * b: the pixel of the bucket with
+ *   bit 0 set and the largest n_nb (before saturation); on equal counts the smallest y wins, then the smallest x; a bucket
+ *   without such a pixel gets (-1, -1, 0).  The first min(buckets, bucket_capacity[s]) entries are written and nothing
+ *   behind them is touched; n_buckets of the record is complete.  bucket_out NULL: no buckets, bucket_w, bucket_h and
+ *   bucket_capacity are not looked at and n_buckets is 0.
+ *
+ * mld_coverage_maps_create: an object bound to `ctx` (its stream, its device) for calls of n_seq (1 .. 65536) sequences.
+ *   params, camera and T_cam_lidar (row-major 3x4) are copied: pass the values the context was created with.  All memory
+ *   is allocated here, none per call; with WW = ceil(W / 64):
+ *     device  112 * n_seq bytes                 (the descriptors)
+ *             24 * WW * H * n_seq bytes         (three bit planes: a row is WW 64-bit words)
+ *             16 * (ceil(WW * H / 16) + ceil(W / 256) * ceil(H / BR)) * n_seq bytes   (block partials of the record; BR =
+ *                                               16 rows, 8 where the wide window can span more than 16 rows)
+ *             2 * W * H * n_seq bytes           (bucket partials: the unsaturated n_nb of the pixels with bit 0)
+ *     pinned  16 * 112 * n_seq bytes            (the descriptor ring)
+ *   The size is checked before the context is looked at, then the context, then params, camera and T_cam_lidar (null),
+ *   and then, still without a use of the context:
+ *     the refusals of mld_create for a parameter set, an image size and a transform, with its status codes
+ *     MLD_ERR_CAPACITY          a wide window that can span more than 64 columns or more than 64 rows, counted as
+ *                               min(W, floor(2 halfX2) + 2) and min(H, floor(2 halfY2) + 2) (C0: 14 x 15): the part of a
+ *                               window in a row lies in at most two words
+ *     MLD_ERR_CAPACITY          n_seq sequences of an image that need more than 2^31 - 1 blocks
+ *   Returns NULL on failure with the reason in *status_out (optional) and the text in
+ *   mld_coverage_maps_last_error(NULL).  Destroy the object before its context.
+ *
+ * mld_coverage_maps_collect_device: HOST tables of n_seq entries, consumed before the call returns; every array they name
+ * is DEVICE memory, naturally aligned for its element type.
+ *   map[s]              W * H int32, index x + y * W: the visible index, or -1.  Every sequence has one.
+ *   index[s], index_len[s], cam[s], n_points[s], coeffs, mask_dev   as mld_feature_traces_collect_device takes them
+ *   bucket_w, bucket_h  1 .. 65535 each;  bucket_capacity[s] >= 0 entries of bucket_out[s] (NULL with capacity 0)
+ *   Asynchronous on the context's stream: no synchronisation, no host read of device data, no runtime call per sequence,
+ *   nothing allocated per call, no atomics, four launches: the descriptor upload, k_coverage_classify (cells into bit
+ *   planes; the map and the index are read once, here), k_coverage_count (window counts, the maps, reach; every requested
+ *   output is written once) and k_coverage_finish (the record from block partials, the buckets).  The device arrays must
+ *   stay valid until the work has run.  Like a context, the object serves one call at a time.
+ *   MLD_ERR_INVALID_ARG with a text naming the function and the argument (mld_coverage_maps_last_error; "null object
+ *   (cm)" of NULL for a null object) on: a null object, a null table map, index, index_len, cam or n_points, a null or
+ *   misaligned record_out_dev, coeffs without mask_dev or the other way round, with bucket_out a bucket_w or bucket_h
+ *   outside 1 .. 65535 or a null table bucket_capacity, a negative count, a null map array (index, cam: where index_len[s],
+ *   n_points[s] > 0; bucket_out[s]: where bucket_capacity[s] > 0), an int32 array that is not 4-byte aligned, an f64 array
+ *   that is not 8-byte aligned.  MLD_ERR_CAPACITY on n_points[s] or index_len[s] beyond 8 388 607 and on buckets so small
+ *   that the call needs more than 2^31 - 1 blocks.
+ */
+enum { MLD_COVERAGE_REACH_MAIN = 1, MLD_COVERAGE_REACH_ROAD = 2 };
+enum { MLD_COVERAGE_FLAG_BAD_INPUT = 1, MLD_COVERAGE_FLAG_HAS_PLANE = 2 };
+
+typedef struct mld_coverage_record {    /* 64 bytes, 8-byte aligned */
+    int64_t n_reach;        /* pixels with bit 0 of reach */
+    int64_t n_reach_road;   /* pixels with bit 1 of reach */
+    int64_t n_occupied, n_inlier, n_far;  /* cells of the map */
+    int32_t max_nb;         /* the largest n_nb of a pixel, before saturation */
+    int32_t flags;          /* MLD_COVERAGE_FLAG_* */
+    int32_t n_buckets;      /* ceil(W / bucket_w) * ceil(H / bucket_h) of the call; 0 without buckets */
+    int32_t pad_[3];
+} mld_coverage_record;
+
+typedef struct mld_coverage_maps mld_coverage_maps;
+mld_coverage_maps* mld_coverage_maps_create(mld_ctx* ctx, int n_seq, const mld_params* params, const mld_camera* camera,
+                                            const double T_cam_lidar[12], int* status_out);
+void mld_coverage_maps_destroy(mld_coverage_maps* cm);
+const char* mld_coverage_maps_last_error(const mld_coverage_maps* cm);
+int mld_coverage_maps_collect_device(mld_coverage_maps* cm, const int32_t* const* map, const int32_t* const* index,
+                                     const int64_t* index_len, const double* const* cam, const int64_t* n_points,
+                                     const float* coeffs, const uint32_t* const* mask_dev, uint8_t* const* nb_out,
+                                     uint8_t* const* road_out, uint8_t* const* road_inl_out, uint8_t* const* road_far_out,
+                                     uint8_t* const* reach_out, mld_coverage_record* record_out_dev, int bucket_w, int bucket_h,
+                                     const int64_t* bucket_capacity, int32_t* const* bucket_out);
+
+/*
  * Debug / parity getters (host buffers; each synchronises).
  *   mld_get_visible_count           -> _points_cs_image_visible.cols()         (DepthEstimator.cpp:192)
  *   mld_get_visible_image_points    -> getPointsCloudImageCs, 2 x Nvis col-major (:392-394)

@@ -164,6 +164,18 @@ class MldFeatureTrace(C.Structure):
                 ("corners", C.c_double * 9)]
 
 
+# mld_coverage_maps: the bits of reach_out and mld_coverage_record::flags (include/mld.h)
+MLD_COVERAGE_REACH_MAIN, MLD_COVERAGE_REACH_ROAD = 1, 2
+MLD_COVERAGE_FLAG_BAD_INPUT, MLD_COVERAGE_FLAG_HAS_PLANE = 1, 2
+
+
+class MldCoverageRecord(C.Structure):
+    """mld_coverage_record (include/mld.h): one sequence of mld_coverage_maps_collect_device, 64 bytes = 8 int64."""
+    _fields_ = [("n_reach", C.c_int64), ("n_reach_road", C.c_int64), ("n_occupied", C.c_int64), ("n_inlier", C.c_int64),
+                ("n_far", C.c_int64), ("max_nb", C.c_int32), ("flags", C.c_int32), ("n_buckets", C.c_int32),
+                ("pad_", C.c_int32 * 3)]
+
+
 # Every symbol include/mld.h declares: (name, restype, argtypes)
 _P = C.POINTER
 _SIGNATURES = [
@@ -285,6 +297,12 @@ _SIGNATURES = [
     ("mld_feature_traces_collect_tracks_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 2 + [_P(C.c_int64)] +
      [_P(C.c_void_p)] * 2 + [_P(C.c_int64), _P(C.c_void_p), _P(C.c_int64), _P(C.c_float), _P(C.c_void_p), C.c_int] +
      [_P(C.c_void_p)] * 5),
+    ("mld_coverage_maps_create", C.c_void_p, [C.c_void_p, C.c_int, _P(MldParams), _P(MldCamera), _P(C.c_double), _P(C.c_int)]),
+    ("mld_coverage_maps_destroy", None, [C.c_void_p]),
+    ("mld_coverage_maps_last_error", C.c_char_p, [C.c_void_p]),
+    ("mld_coverage_maps_collect_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 2 + [_P(C.c_int64), _P(C.c_void_p),
+                                                   _P(C.c_int64), _P(C.c_float)] + [_P(C.c_void_p)] * 6 +
+     [C.c_void_p, C.c_int, C.c_int, _P(C.c_int64), _P(C.c_void_p)]),
     ("mld_get_visible_count", C.c_int, [C.c_void_p, C.c_int, _P(C.c_int64)]),
     ("mld_get_visible_image_points", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
     ("mld_get_point_index", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),

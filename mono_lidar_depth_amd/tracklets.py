@@ -170,7 +170,7 @@ class TrackletDepthModule:
 
 
 class _BatchObject:
-    """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes, ProjectedClouds, DepthReports, PlaneInliers and FeatureTraces share: an object of the C-ABI (mld_<_NAME>_create /
+    """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes, ProjectedClouds, DepthReports, PlaneInliers, FeatureTraces and CoverageMaps share: an object of the C-ABI (mld_<_NAME>_create /
     _destroy / _last_error) on an estimator's context, its handle in the attribute named _HANDLE, and the tensors of
     the calls that may still be queued."""
 
@@ -831,6 +831,97 @@ class FeatureTraces(_BatchObject):
         self._collect(ns, (u, v), pixel_map, index, cam, trace, coeffs, masks, list_capacity, (nb, seg, road, road_inl))
 
 
+class CoverageMaps(_BatchObject):
+    """Where in the image a feature can get a depth, for S sequences per call (mld_coverage_maps_*, include/mld.h): at
+    every integer pixel the neighbour counts of the narrow and the wide window (occupied, plane inliers, far points),
+    the two reach bits - the feature is not type 2; the road estimator can run -, per sequence a record of totals, and
+    per bucket of the image the pixel with the most neighbours.  It runs on the tensors ProjectedClouds.export wrote
+    (pixel_map, index, cam) and on the planes as prepare() / prepare_step() take them.  `parameters` (default: the
+    estimator's) is copied at creation.  Lists of S torch CUDA tensors in and out; asynchronous on the estimator's
+    stream.  Close it before its estimator."""
+
+    _NAME, _HANDLE = "coverage_maps", "_cm"
+    WORDS = 8  # int64 words of a record (capi.MldCoverageRecord, 64 bytes)
+    DTYPE = np.dtype(capi.MldCoverageRecord)
+    MAPS = ("nb", "road", "road_inl", "road_far", "reach")
+
+    def __init__(self, estimator: DepthEstimator, n_seq: int, parameters=None):
+        self.S = int(n_seq)
+        P = parameters if parameters is not None else estimator.getParameters()
+        cam = estimator._camera.as_struct()
+        self.width, self.height = int(cam.width), int(cam.height)
+        T = np.ascontiguousarray(np.asarray(estimator._T, dtype=np.float64).reshape(-1)[:12])
+        self._create(estimator, self.S, C.byref(P), C.byref(cam), T.ctypes.data_as(C.POINTER(C.c_double)))
+
+    @classmethod
+    def records(cls, record) -> np.ndarray:
+        """A record tensor (int64 [S, 8]) as a NumPy record array with the fields of capi.MldCoverageRecord (copies to
+        the host, which synchronises as usual)."""
+        return np.ascontiguousarray(record.cpu().numpy()).reshape(-1).view(cls.DTYPE)
+
+    def buckets(self, bucket_w: int, bucket_h: int) -> int:
+        """Buckets of the image for buckets of this size: ceil(width / bucket_w) * ceil(height / bucket_h)."""
+        return -(-self.width // int(bucket_w)) * -(-self.height // int(bucket_h))
+
+    def collect(self, pixel_map, index, cam, record, coeffs=None, masks=None, nb=None, road=None, road_inl=None, road_far=None,
+                reach=None, bucket=None, bucket_out=None):
+        """pixel_map, index, cam: the S tensors each that ProjectedClouds.export wrote for the clouds (int32 [height,
+        width], int32 of a capacity that did not truncate, float64 [points, 3]; index and cam entries may be None for an
+        empty cloud); record: an int64 CUDA tensor of at least 8 * S entries (a contiguous [S, 8]:
+        capi.MldCoverageRecord, see records()); coeffs (float32 [S, 4], host) and masks (S int32 CUDA tensors, an entry
+        None: that sequence has no plane): both or neither; nb, road, road_inl, road_far, reach: None, or S uint8 CUDA
+        tensors of at least width * height entries (a contiguous [height, width]; single entries may be None); bucket:
+        None or (bucket_w, bucket_h) with bucket_out: S int32 CUDA tensors (a contiguous [capacity, 3] each, rows (x, y,
+        n_nb); an entry None: capacity 0).  A sequence's first min(buckets, capacity) rows are written; n_buckets of the
+        record is complete."""
+        S, cells = self.S, self.width * self.height
+        maps = (nb, road, road_inl, road_far, reach)
+        for name, ts in (("pixel_map", pixel_map), ("index", index), ("cam", cam), ("masks", masks), ("bucket_out", bucket_out)) + \
+                tuple(zip(self.MAPS, maps)):
+            if ts is not None and len(ts) != S:
+                raise ValueError(f"{name}: expected {S} entries, one per sequence")
+        if (coeffs is None) != (masks is None):
+            raise ValueError("coeffs and masks come together or not at all")
+        if (bucket is None) != (bucket_out is None):
+            raise ValueError("bucket and bucket_out come together or not at all")
+
+        def holds(t, s, entries, size, name):
+            if t is None:
+                raise ValueError(f"sequence {s}: {name} is missing")
+            if t.element_size() != size or not t.is_contiguous() or int(t.numel()) < entries:
+                raise ValueError(f"sequence {s}: {name} must be contiguous, of {size}-byte elements, at least {entries} of them")
+
+        holds(record, "*", self.WORDS * S, 8, "record")
+        n_idx, n_pts, caps = [], [], []
+        for s in range(S):
+            holds(pixel_map[s], s, cells, 4, "pixel_map")
+            if index[s] is not None:
+                holds(index[s], s, 0, 4, "index")
+            if cam[s] is not None:
+                holds(cam[s], s, 0, 8, "cam")
+            n_idx.append(int(index[s].numel()) if index[s] is not None else 0)
+            n_pts.append(int(cam[s].numel()) // 3 if cam[s] is not None else 0)
+            for name, ts in zip(self.MAPS, maps):
+                if ts is not None and ts[s] is not None:
+                    holds(ts[s], s, cells, 1, name)
+            if bucket_out is not None:
+                if bucket_out[s] is not None:
+                    holds(bucket_out[s], s, 0, 4, "bucket_out")
+                caps.append(int(bucket_out[s].numel()) // 3 if bucket_out[s] is not None else 0)
+        co = None
+        if coeffs is not None:
+            co = np.ascontiguousarray(coeffs, dtype=np.float32).reshape(S, 4)
+        bw, bh = (int(bucket[0]), int(bucket[1])) if bucket is not None else (0, 0)
+        vp = self._ptrs
+        self._check(self._lib.mld_coverage_maps_collect_device(
+            self._cm, vp(pixel_map), vp(index), (C.c_int64 * S)(*n_idx), vp(cam), (C.c_int64 * S)(*n_pts),
+            co.ctypes.data_as(C.POINTER(C.c_float)) if co is not None else None, vp(masks) if masks is not None else None,
+            *[vp(ts) if ts is not None else None for ts in maps], int(record.data_ptr()), bw, bh,
+            (C.c_int64 * S)(*caps) if bucket_out is not None else None, vp(bucket_out) if bucket_out is not None else None))
+        self._hold((list(pixel_map), list(index), list(cam), record, list(masks) if masks is not None else None,
+                    [list(ts) if ts is not None else None for ts in maps], list(bucket_out) if bucket_out is not None else None))
+
+
 class TrackletBatch:
     """The tracklet layer for S independent sequences at once (mld_set_clouds_planes_range_device +
     mld_tracklets_depths_device): the estimator's frame slots are two banks of S slots, sequence s keeps its current
@@ -865,6 +956,7 @@ class TrackletBatch:
         self.depth_reports: Optional[DepthReports] = None
         self.inliers: Optional[PlaneInliers] = None
         self.feature_traces: Optional[FeatureTraces] = None
+        self.coverage_maps: Optional[CoverageMaps] = None
 
     @property
     def have_last(self) -> bool:
@@ -1122,6 +1214,46 @@ class TrackletBatch:
         self.est.orderTorchAfter()
         return out
 
+    def attach_coverage(self) -> CoverageMaps:
+        """The coverage maps of the S sequences that coverage() runs.  It takes the estimator's parameters as they are
+        now."""
+        if self.coverage_maps is None:
+            self.coverage_maps = CoverageMaps(self.est, self.S)
+        return self.coverage_maps
+
+    def coverage(self, clouds, coeffs=None, masks=None, maps=CoverageMaps.MAPS, bucket=None, capacity=None):
+        """Where a feature of this frame can get a depth: CoverageMaps.collect on `clouds`, the dict
+        projected_clouds(cam=True, pixel_map=True) returned for this frame's clouds with a capacity that did not
+        truncate, and on the planes as prepare() / prepare_step() take them (coeffs float32 [S, 4] on the host, masks S
+        int32 CUDA tensors; both None: without planes).  maps: which of nb, road, road_inl, road_far and reach to make;
+        bucket: None or (bucket_w, bucket_h); capacity: S integers, or None (= every bucket).  Returns a dict with record
+        (int64 [S, 8]: capi.MldCoverageRecord, see CoverageMaps.records()), the maps asked for (S uint8 [height, width]
+        each, the others None) and buckets (S int32 [capacity, 3], rows (x, y, n_nb), or None).  No synchronisation:
+        torch's current stream is made to wait for the call; a host read synchronises as usual.  attach_coverage()
+        first."""
+        import torch
+        if self.coverage_maps is None:
+            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.coverage without attach_coverage")
+        if clouds.get("cam") is None or clouds.get("pixel_map") is None:
+            raise ValueError("clouds: projected_clouds(cam=True, pixel_map=True) of this frame")
+        cm = self.coverage_maps
+        unknown = [m for m in maps if m not in CoverageMaps.MAPS]
+        if unknown:
+            raise ValueError(f"maps: unknown {unknown}")
+        dev = clouds["pixel_map"][0].device
+        out = {"record": torch.empty((self.S, CoverageMaps.WORDS), dtype=torch.int64, device=dev), "buckets": None}
+        for name in CoverageMaps.MAPS:
+            out[name] = [torch.empty((cm.height, cm.width), dtype=torch.uint8, device=dev) for _ in range(self.S)] if name in maps else None
+        if bucket is not None:
+            nb = cm.buckets(*bucket)
+            caps = [min(int(capacity[s]), nb) if capacity is not None else nb for s in range(self.S)]
+            out["buckets"] = [torch.empty((m, 3), dtype=torch.int32, device=dev) for m in caps]
+        self.est._after_torch(clouds["pixel_map"][0])
+        cm.collect(clouds["pixel_map"], clouds["index"], clouds["cam"], out["record"], coeffs, masks,
+                   *[out[name] for name in CoverageMaps.MAPS], bucket=bucket, bucket_out=out["buckets"])
+        self.est.orderTorchAfter()
+        return out
+
     def attach_labels(self) -> SemanticLabels:
         """The label assignment of the S sequences that labels() queues behind a step."""
         if self.semantic_labels is None:
@@ -1252,4 +1384,7 @@ class TrackletBatch:
         if self.feature_traces is not None:
             self.feature_traces.close()
             self.feature_traces = None
+        if self.coverage_maps is not None:
+            self.coverage_maps.close()
+            self.coverage_maps = None
         self.est.close()
