@@ -504,6 +504,9 @@ int mld_tracklets_depths_lanes_device(mld_ctx* ctx, int n_seq, int bank_cur, con
  *   mld_tracks_export_device  convert_tracklets_to_matches_msg (:209-259): the stored tracks in message order
  *   mld_tracks_export_packed_device  the same tracks back to back, every track with exactly its stored entries, and
  *                             the offsets at which they start (what the message holds: `curTracklet.size()` points each)
+ *   mld_tracks_export_leaving_device  between a begin and its commit: the tracks TidyUpTracklets is about to erase, whole,
+ *                             and the entries the max_history cap is about to drop; mld_tracks_set_leaving_sink: the same
+ *                             from inside the next step call
  *   mld_tracks_import_packed_device  the inverse of the packed export: the committed frame of the selected sequences
  *                             replaced by given tracks, as if a fresh TrackletDepthModule had been brought to that state
  *                             (the reference has no checkpoint / resume: SURVEY 5); mld_tracks_reset_device: by no tracks
@@ -522,12 +525,13 @@ int mld_tracklets_depths_lanes_device(mld_ctx* ctx, int n_seq, int bank_cur, con
  *   max_tracks : tracks per frame and sequence the store sustains indefinitely at any churn (every track replaced
  *                every frame included): the rows of the tracks that ended are taken back before new ones are handed out.
  *   max_history: >= 2; stored entries per track.  DEVIATION: the reference's deque is unbounded, here the oldest entries
- *                fall off - results equal the reference whenever no track outlives max_history frames.
+ *                fall off - results equal the reference whenever no track outlives max_history frames.  An archive that
+ *                takes mld_tracks_export_leaving_device's spilled entries before every commit loses nothing.
  *   All memory is allocated here, none per frame.  Device bytes with cap = the power of two >= 2 * max_tracks:
  *     n_seq * (max_tracks * (12 * max_history + 45) + 16 * cap + 132 + 12 * ceil(max_tracks / 256))
  *   (histories 12 * max_history per track: 0.49 GB of 0.74 GB for 256 sequences x 10 000 tracks x 16 entries; 4 of the 45
  *   bytes per track and the last term are the scratch of the packed export's scan: length and ring head per track, a
- *   32-bit sum and a 64-bit base per block of 256 tracks), plus max_tracks bytes once (the all-zero mask of
+ *   32-bit sum and a 64-bit base per block of 256 tracks; the leaving export works in the same scratch), plus max_tracks bytes once (the all-zero mask of
  *   mld_tracklets_step_lanes_device) and 16 * 96 * n_seq bytes of pinned host memory.
  *   Returns NULL on failure with the reason in *status_out (optional) and the text in mld_tracks_last_error(NULL).
  *   Destroy the store before its context.
@@ -560,6 +564,51 @@ int mld_tracklets_depths_lanes_device(mld_ctx* ctx, int n_seq, int bank_cur, con
  *   touched; the offsets are complete all the same, so offsets[n] > capacity[s] tells a truncated sequence.
  *   capacity[s] = n_tracks[s] * max_history never truncates.  A sequence without tracks needs no arrays and gets nothing
  *   written; a capacity of 0 needs no fp_out[s].  Any other null array of a sequence with tracks is refused.  Asynchronous, no synchronisation, no host read of device data, nothing allocated per call.
+ *
+ * mld_tracks_export_leaving_device: what the commit of the BEGUN frame removes from the store, read between
+ *   mld_tracks_begin_device and mld_tracks_commit_device (read-only; any number of calls, the commit is not affected).
+ *   Per sequence s the stored tracks of the last committed frame are walked in that frame's (message) order;
+ *   occurrences of a repeated id that lost are skipped, the stored occurrence stands for them.
+ *   DEVIATION (order): the reference iterates its std::map, i.e. by ascending id (TidyUpTracklets :171-193); here both
+ *   streams come in the committed frame's order.
+ *   Ended tracks - tracks the begun frame's look-up did not find, which the commit erases: ids_out[s][k] = the id,
+ *   offsets_out[s][k] = the sum of the stored lengths of the ended tracks in front of track k (int64), fp_out[s] = their
+ *   entries back to back, (u, v, d) float32, newest first - per track the layout and the bits
+ *   mld_tracks_export_packed_device writes for the same track.
+ *   Spilled entries - for every track that continues with max_history stored entries, the oldest one, which the
+ *   commit's push overwrites: spill_ids_out[s][k] = the id, spill_fp_out[s][3 * k ..] = the entry.  Tracks shorter than
+ *   max_history spill nothing.  With both streams a consumer that appends the spilled entries to a track's tail and
+ *   closes the track when it ends holds every track once and complete: the reference's unbounded deque at the moment
+ *   TidyUpTracklets erases it (the max_history DEVIATION of mld_tracks_create loses nothing for such a consumer).
+ *   flush (host, n_seq flags; NULL: none): a flagged sequence treats every stored track as ended, whatever the marks
+ *   say, and spills nothing - the end of a recording, or a lane about to be restarted or reset.  When every sequence is
+ *   flagged no begun frame is needed; otherwise a call without one returns MLD_ERR_NOT_INITIALIZED (a begin abandoned by
+ *   an import counts as none).
+ *   Capacities (host, n_seq each, >= 0): track_capacity[s] tracks in ids_out[s] and track_capacity[s] + 1 entries in
+ *   offsets_out[s]; entry_capacity[s] entries in fp_out[s]; spill_capacity[s] entries in spill_ids_out[s] and
+ *   spill_fp_out[s].  With w = min(n_ended, track_capacity[s]): ids_out[s][0 .. w-1] and offsets_out[s][0 .. w] are
+ *   written (offsets[w] closes track w - 1; with track_capacity[s] == 0 nothing of either), entries at positions below
+ *   min(n_ended_entries, entry_capacity[s]) whichever track they belong to, spills below min(n_spilled,
+ *   spill_capacity[s]); nothing at or beyond these is touched.  n_committed, n_committed * max_history and n_committed -
+ *   the track count of the last committed frame, which the host knows - never truncate.
+ *   record_out_dev: n_seq mld_leaving_record in device memory, 8-byte aligned; every record is written completely by
+ *   every call and its counts are complete, so n_ended > track_capacity[s] (and so on) tells a truncated sequence.  A
+ *   sequence without committed tracks gets a record of zeros, needs no arrays and gets nothing else written.
+ *   MLD_ERR_INVALID_ARG with "mld_tracks_export_leaving_device: <argument>" for a null table (all but flush are
+ *   required), a null array of a sequence with committed tracks whose capacity is > 0, a negative capacity, an array
+ *   that is not aligned to its element (offsets_out and record_out_dev: 8 bytes, the others 4); everything is checked
+ *   before anything is queued.  Asynchronous, no synchronisation, no host read of device data, nothing allocated per
+ *   call, no atomics (both streams are deterministic): three launches behind the descriptor upload, in the scratch of
+ *   the packed export.
+ *
+ * mld_tracks_set_leaving_sink: the output arguments of mld_tracks_export_leaving_device for the NEXT
+ *   mld_tracklets_step_device / mld_tracklets_step_lanes_device on the store, whose begin and commit lie inside one call.
+ *   The tables are copied; the device arrays must stay valid until that step has run.  That step writes every
+ *   sequence's record and streams in exactly one of two passes: a restarting sequence is flushed BEFORE it is emptied,
+ *   every other sequence is exported by the marks AFTER the step's look-up.  The sink is then disarmed; a step that is
+ *   refused before its look-up writes nothing and leaves it armed; a step that fails later has consumed it.  Checks as
+ *   above, except that an array may be null only where its capacity is 0 (the step's track counts are not known yet).
+ *   All arguments NULL disarms.  Without a sink a step queues exactly the launches it queues without this function.
  *
  * mld_tracks_import_packed_device: per sequence s with select[s] != 0 (select: host, n_seq flags; NULL: every sequence)
  *   the committed frame is replaced by the n_tracks[s] given tracks in the given (message) order: track i has id
@@ -619,6 +668,19 @@ int mld_tracks_export_packed_device(mld_tracks* tr, float* const* fp_out, const 
 int mld_tracks_import_packed_device(mld_tracks* tr, const uint8_t* select, const int32_t* const* ids, const int64_t* n_tracks,
                                     const int64_t* const* offsets, const float* const* fp, const int64_t* n_entries);
 int mld_tracks_reset_device(mld_tracks* tr, const uint8_t* select);
+typedef struct mld_leaving_record {
+    int64_t n_ended;          /* stored tracks of the committed frame that end */
+    int64_t n_ended_entries;  /* their entries */
+    int64_t n_spilled;        /* continuing tracks whose oldest entry is overwritten */
+    int64_t reserved;         /* 0 */
+} mld_leaving_record;         /* 32 bytes */
+int mld_tracks_export_leaving_device(mld_tracks* tr, const uint8_t* flush, int32_t* const* ids_out, int64_t* const* offsets_out,
+                                     float* const* fp_out, int32_t* const* spill_ids_out, float* const* spill_fp_out,
+                                     const int64_t* track_capacity, const int64_t* entry_capacity, const int64_t* spill_capacity,
+                                     void* record_out_dev);
+int mld_tracks_set_leaving_sink(mld_tracks* tr, int32_t* const* ids_out, int64_t* const* offsets_out, float* const* fp_out,
+                                int32_t* const* spill_ids_out, float* const* spill_fp_out, const int64_t* track_capacity,
+                                const int64_t* entry_capacity, const int64_t* spill_capacity, void* record_out_dev);
 int mld_tracks_counts(mld_tracks* tr, int64_t* counts_out);
 int mld_tracklets_step_device(mld_ctx* ctx, mld_tracks* tr, int bank_cur, int have_last, const int32_t* const* ids,
                               const float* const* u_new, const float* const* v_new, const float* const* u_old,

@@ -144,6 +144,11 @@ class MldDepthReport(C.Structure):
     _fields_ = [("counts", C.c_int64 * MLD_RESULT_TYPE_COUNT), ("other", C.c_int64), ("point_count", C.c_int64), ("n_interpolated", C.c_int64)]
 
 
+class MldLeavingRecord(C.Structure):
+    """mld_leaving_record (include/mld.h): one sequence of mld_tracks_export_leaving_device, 32 bytes = 4 int64."""
+    _fields_ = [("n_ended", C.c_int64), ("n_ended_entries", C.c_int64), ("n_spilled", C.c_int64), ("reserved", C.c_int64)]
+
+
 class MldPlaneInlierCounts(C.Structure):
     """mld_plane_inlier_counts (include/mld.h): one sequence of mld_plane_inliers_export_device, 16 bytes = 2 int64."""
     _fields_ = [("n_inliers", C.c_int64), ("n_cloud", C.c_int64)]
@@ -251,6 +256,9 @@ _SIGNATURES = [
     ("mld_tracks_import_packed_device", C.c_int, [C.c_void_p, _P(C.c_uint8), _P(C.c_void_p), _P(C.c_int64), _P(C.c_void_p),
                                                   _P(C.c_void_p), _P(C.c_int64)]),
     ("mld_tracks_reset_device", C.c_int, [C.c_void_p, _P(C.c_uint8)]),
+    ("mld_tracks_export_leaving_device", C.c_int, [C.c_void_p, _P(C.c_uint8)] + [_P(C.c_void_p)] * 5 + [_P(C.c_int64)] * 3 +
+     [C.c_void_p]),
+    ("mld_tracks_set_leaving_sink", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 5 + [_P(C.c_int64)] * 3 + [C.c_void_p]),
     ("mld_tracks_counts", C.c_int, [C.c_void_p, _P(C.c_int64)]),
     ("mld_tracklets_step_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [_P(C.c_void_p)] * 5 +
      [_P(C.c_int64)] + [_P(C.c_void_p)] * 4),

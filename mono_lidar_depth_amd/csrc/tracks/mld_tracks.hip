@@ -32,6 +32,8 @@
 //                      table with atomicCAS, then pushes its entries
 //   k_tracks_export / k_tracks_count   read-only
 //   k_tracks_pack_sums / _scan / _write   read-only: the packed export, tracks back to back with offsets (below)
+//   k_tracks_leave_sums / _scan / _write  read-only, between a look-up and its commit: the tracks that commit erases and
+//                      the entries it overwrites (at the kernels)
 //   k_tracks_reset / k_tracks_import      the packed import, the inverse of that export, for selected sequences: the
 //                      committed table and the pool as created, then insert + fill (at the kernels); the reset alone
 //                      empties sequences (mld_tracks_reset_device, the restart of mld_tracklets_step_lanes_device)
@@ -72,17 +74,32 @@ constexpr unsigned long long kOccupied = 1ull << 63;
 // One sequence of one call.  Host-made, staged through the descriptor ring (mld_batch::DescRing), read by every kernel
 // of the call.
 struct TrSeq {
-    const int32_t* ids;
-    uint8_t* is_new;
-    const float* u_new;
-    const float* v_new;
-    const float* u_old;
+    union {
+        const int32_t* ids;
+        int32_t* ids_out;  // mld_tracks_export_leaving_device (as every second member of the unions down to u_old)
+    };
+    union {
+        uint8_t* is_new;
+        int32_t* spill_ids_out;
+    };
+    union {
+        const float* u_new;
+        float* spill_fp_out;
+    };
+    union {
+        const float* v_new;
+        int64_t track_capacity;  // tracks ids_out holds; offsets_out holds one more entry
+    };
+    union {
+        const float* u_old;
+        int64_t spill_capacity;  // entries spill_ids_out / spill_fp_out hold
+    };
     const float* v_old;
     const float* d_cur;
     union {
         const float* d_last;
         float* d_last_w;    // mld_tracklets_step_lanes_device: d_last_out of a sequence without a previous frame
-        int64_t capacity;   // mld_tracks_export_packed_device: entries fp_out holds
+        int64_t capacity;   // mld_tracks_export_packed_device, mld_tracks_export_leaving_device: entries fp_out holds
         int64_t n_entries;  // mld_tracks_import_packed_device: entries fp_in holds
     };
     union {
@@ -95,7 +112,10 @@ struct TrSeq {
         const int64_t* offsets_in;  // mld_tracks_import_packed_device
     };
     int32_t n;          // tracks of the frame the call works on
-    int32_t n_prev;     // tracks of the committed frame (release pass)
+    union {
+        int32_t n_prev;      // tracks of the committed frame (release pass)
+        int32_t leave_mode;  // mld_tracks_export_leaving_device: kLeaveSkip / kLeaveMarks / kLeaveFlush
+    };
     int32_t blk0;       // first block of the sequence in a launch over n (export: over n * max_history)
     int32_t blk0_prev;  // the same for the release pass (at least one block per sequence; reset: over the table's
                         // slots, and none for a sequence that is not selected)
@@ -446,6 +466,165 @@ __global__ __launch_bounds__(kBlock) void k_tracks_pack_write(TrDev T, const TrS
     }
 }
 
+// ---- the leaving export: what the commit of the begun frame removes from the store ----
+//
+// Between a look-up and its commit, of every stored track of the committed frame (slot >= 0):
+//   ended    mark != epoch (or the sequence is flushed): k_tracks_release hands its row back; id, offset and entries go
+//            out as the packed export writes them
+//   spilled  mark == epoch and len == max_history: k_tracks_commit's push_front overwrites the oldest entry, ring
+//            position head + H - 1; id and that entry go out
+// The packed export's three kernels with three columns (ended tracks, their entries, spilled tracks) in place of one,
+// on the same flat (sequence, chunk of 256 committed tracks) blocks and in the same scratch (the store serves one call
+// at a time):
+//   pack_meta[track]  ended: length | head << 16;  spilled: kLeaveSpill | the oldest entry's ring position;  neither:
+//                     kLeaveNone.  (head and ring positions are below max_history <= 65535: the upper half 0xffff is
+//                     no head.)
+//   pack_base[block]  sums -> scan: ended | spilled << 10 | entries << 20 (at most 256, 256 and 256 * 65535)
+//                     scan -> write: entries of the sequence in front of the block (40 bits: below 2^24 * 65535) |
+//                     ended tracks in front of it << 40 (below max_tracks <= 2^24)
+//   pack_sum[block]   scan -> write: spilled tracks of the sequence in front of the block
+// No atomics: the order of both streams is the committed frame's.  No block waits on another.
+constexpr uint32_t kLeaveNone = 0xffffffffu;
+constexpr uint32_t kLeaveSpill = 0xffff0000u;
+constexpr int kLeaveSkip = 0, kLeaveMarks = 1, kLeaveFlush = 2;  // TrSeq::leave_mode (skip: n = 0, the record stays)
+
+__global__ __launch_bounds__(kBlock) void k_tracks_leave_sums(TrDev T, const TrSeq* __restrict__ desc, int cur, uint32_t epoch) {
+    __shared__ unsigned long long s_wave[kBlock / 64];
+    const int s = seq_of_block<false>(desc, T.n_seq, (int)blockIdx.x);
+    const TrSeq& q = desc[s];
+    const int i = ((int)blockIdx.x - q.blk0) * kBlock + (int)threadIdx.x;
+    unsigned long long sum = 0;
+    if (i < q.n) {
+        const size_t ps = ((size_t)cur * T.n_seq + s) * T.M + (size_t)i;
+        const size_t base = (size_t)s * T.M;
+        uint32_t meta = kLeaveNone;
+        if (T.slot[ps] >= 0) {  // (a repeated id that lost: the stored occurrence stands for it)
+            const int row = T.row[ps];
+            const uint32_t len = (uint32_t)T.len[base + row], head = (uint32_t)T.head[base + row];
+            if (q.leave_mode == kLeaveFlush || T.mark[base + row] != epoch) {
+                meta = len | (head << 16);
+                sum = 1ull | ((unsigned long long)len << 20);
+            } else if (len == (uint32_t)T.H) {
+                uint32_t oldest = head + (uint32_t)T.H - 1u;
+                if (oldest >= (uint32_t)T.H) oldest -= (uint32_t)T.H;
+                meta = kLeaveSpill | oldest;
+                sum = 1ull << 10;
+            }
+        }
+        T.pack_meta[base + i] = meta;
+    }
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long all = 0;
+        for (int k = 0; k < kBlock / 64; k++) all += s_wave[k];
+        T.pack_base[blockIdx.x] = all;
+    }
+}
+
+// One block per sequence, as k_tracks_pack_scan; the totals are the sequence's record (three int64 and a zero).
+__global__ __launch_bounds__(kScanWidth) void k_tracks_leave_scan(TrDev T, const TrSeq* __restrict__ desc, long long* __restrict__ record) {
+    __shared__ unsigned long long s_wave[kBlock / 64];
+    const TrSeq& q = desc[blockIdx.x];
+    if (q.leave_mode == kLeaveSkip) return;  // (uniform over the block)
+    const int nb = (q.n + kBlock - 1) / kBlock;
+    unsigned long long carry_ts = 0, carry_e = 0;  // ended tracks | spilled tracks << 32 (both <= 2^24); entries
+    for (int j0 = 0; j0 < nb; j0 += kScanWidth) {
+        const int j = j0 + (int)threadIdx.x;
+        const unsigned long long v = j < nb ? T.pack_base[q.blk0 + j] : 0ull;
+        unsigned long long all_ts, all_e;
+        const unsigned long long before_ts = block_scan_exclusive((v & 0x3ffull) | (((v >> 10) & 0x3ffull) << 32), s_wave, &all_ts);
+        const unsigned long long before_e = block_scan_exclusive(v >> 20, s_wave, &all_e);
+        if (j < nb) {
+            const unsigned long long ts = carry_ts + before_ts;
+            T.pack_base[q.blk0 + j] = (carry_e + before_e) | ((ts & 0xffffffffull) << 40);
+            T.pack_sum[q.blk0 + j] = (uint32_t)(ts >> 32);
+        }
+        carry_ts += all_ts;
+        carry_e += all_e;
+    }
+    if (threadIdx.x == 0) {
+        long long* r = record + (size_t)blockIdx.x * 4;
+        r[0] = (long long)(carry_ts & 0xffffffffull);
+        r[1] = (long long)carry_e;
+        r[2] = (long long)(carry_ts >> 32);
+        r[3] = 0;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_tracks_leave_write(TrDev T, const TrSeq* __restrict__ desc, int cur) {
+    __shared__ uint32_t s_wave[kBlock / 64];
+    __shared__ uint32_t s_off[kBlock + 1];
+    __shared__ int32_t s_row[kBlock], s_head[kBlock];
+    const int s = seq_of_block<false>(desc, T.n_seq, (int)blockIdx.x);
+    const TrSeq& q = desc[s];
+    const int t = (int)threadIdx.x;
+    const int i = ((int)blockIdx.x - q.blk0) * kBlock + t;
+    const size_t base = (size_t)s * T.M;
+    const uint32_t meta = i < q.n ? T.pack_meta[base + i] : kLeaveNone;
+    const bool ended = (meta >> 16) != 0xffffu, spilled = !ended && meta != kLeaveNone;
+    const uint32_t len = ended ? (meta & 0xffffu) : 0u;
+    uint32_t n_flags, total;
+    const uint32_t flags_before = block_scan_exclusive((ended ? 1u : 0u) | (spilled ? 1u << 16 : 0u), s_wave, &n_flags);
+    const uint32_t before = block_scan_exclusive(len, s_wave, &total);
+    const unsigned long long pb = T.pack_base[blockIdx.x];
+    const long long first = (long long)(pb & ((1ull << 40) - 1));  // entries of the sequence's ended tracks in front of this block
+    const long long first_track = (long long)(pb >> 40);
+    const long long first_spill = (long long)T.pack_sum[blockIdx.x];
+    int row = -1;
+    int32_t id = 0;
+    if (ended || spilled) {
+        const size_t ps = ((size_t)cur * T.n_seq + s) * T.M + (size_t)i;
+        row = T.row[ps];
+        id = (int32_t)(uint32_t)T.table[((size_t)cur * T.n_seq + s) * T.cap + (size_t)T.slot[ps]];
+    }
+    s_off[t] = before;
+    s_row[t] = len ? row : -1;
+    s_head[t] = (int32_t)(meta >> 16);
+    if (t == 0) s_off[kBlock] = total;
+    const long long track_cap = (long long)q.track_capacity;
+    if (ended) {
+        const long long k = first_track + (long long)(flags_before & 0xffffu);
+        if (k < track_cap) q.ids_out[k] = id;
+        if (k <= track_cap && track_cap > 0) q.offsets_out[k] = first + (long long)before;  // (k == capacity: the closing entry)
+    }
+    if (t == 0 && (int)blockIdx.x - q.blk0 == (q.n - 1) / kBlock) {  // the closing entry of a sequence that is not truncated
+        const long long n_ended = first_track + (long long)(n_flags & 0xffffu);
+        if (n_ended <= track_cap && track_cap > 0) q.offsets_out[n_ended] = first + (long long)total;
+    }
+    if (spilled) {
+        const long long k = first_spill + (long long)(flags_before >> 16);
+        if (k < (long long)q.spill_capacity) {
+            q.spill_ids_out[k] = id;
+            const float* __restrict__ src = T.hist + ((base + row) * (size_t)T.H + (meta & 0xffffu)) * 3;
+            float* dst = q.spill_fp_out + (size_t)k * 3;
+            dst[0] = src[0];
+            dst[1] = src[1];
+            dst[2] = src[2];
+        }
+    }
+    __syncthreads();
+    const long long room = (long long)q.capacity - first;  // entries of this block's range below the capacity
+    if (!q.fp_out || room <= 0) return;
+    const uint32_t limit = room < (long long)total ? (uint32_t)room : total;
+    float* __restrict__ dst0 = q.fp_out + (size_t)first * 3;
+    for (uint32_t e = (uint32_t)t; e < limit; e += kBlock) {
+        int lo = 0, hi = kBlock;  // the last track whose prefix is <= e (k_tracks_pack_write)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (s_off[mid] <= e) lo = mid; else hi = mid;
+        }
+        int p = s_head[lo] + (int)(e - s_off[lo]);
+        if (p >= T.H) p -= T.H;
+        const float* __restrict__ src = T.hist + ((base + s_row[lo]) * (size_t)T.H + p) * 3;
+        float* dst = dst0 + (size_t)e * 3;
+        dst[0] = src[0];
+        dst[1] = src[1];
+        dst[2] = src[2];
+    }
+}
+
 // ---- the packed import: the inverse of the packed export ----
 
 // The selected sequences as mld_tracks_create left them: the committed table without an id, every row on the free stack
@@ -571,6 +750,19 @@ __global__ __launch_bounds__(kBlock) void k_tracks_no_previous(const TrSeq* __re
 
 char g_create_error[512] = "";
 
+// The output arguments of mld_tracks_export_leaving_device: host tables of n_seq entries, one record array on the device.
+struct LeaveOut {
+    int32_t* const* ids_out;
+    int64_t* const* offsets_out;
+    float* const* fp_out;
+    int32_t* const* spill_ids_out;
+    float* const* spill_fp_out;
+    const int64_t* track_capacity;
+    const int64_t* entry_capacity;
+    const int64_t* spill_capacity;
+    void* record;
+};
+
 }  // namespace
 
 struct mld_tracks : mld_batch::Object {
@@ -588,6 +780,14 @@ struct mld_tracks : mld_batch::Object {
     std::vector<uint8_t*> mask_pending;
     std::vector<const uint8_t*> mask_table;  // mld_tracklets_step_device
     std::vector<uint8_t> lane_last;          // mld_tracklets_step_lanes_device: have_last of the lanes that do not restart
+    // mld_tracks_set_leaving_sink: copies of the caller's tables, `sink` points at them; consumed by the next step
+    bool sink_armed = false;
+    LeaveOut sink{};
+    std::vector<int32_t*> sink_ids, sink_spill_ids;
+    std::vector<int64_t*> sink_offsets;
+    std::vector<float*> sink_fp, sink_spill_fp;
+    std::vector<int64_t> sink_caps;          // [3][n_seq]: tracks, entries, spills
+    std::vector<uint8_t> leave_mode;         // the step's two passes over the sink
 };
 
 namespace {
@@ -619,6 +819,84 @@ int check_begin(mld_tracks* tr, const char* fn, const int32_t* const* ids, const
         if (n_tracks[s] < 0) return refuse(MLD_ERR_INVALID_ARG, "negative track count");
         if (n_tracks[s] > tr->d.M) return refuse(MLD_ERR_CAPACITY, "more tracks than max_tracks");
         if (n_tracks[s] > 0 && (!ids[s] || (is_new_out && !is_new_out[s]))) return refuse(MLD_ERR_INVALID_ARG, "null array");
+    }
+    return MLD_OK;
+}
+
+// What mld_tracks_export_leaving_device refuses, without a change of state.  every_sequence: an array may be null only
+// where its capacity is 0 (the sink: the track counts of the step that consumes it are not known yet); otherwise also
+// where the sequence has no committed track.
+int check_leaving(mld_tracks* tr, const char* fn, const LeaveOut& o, bool every_sequence) {
+    auto refuse = [&](const std::string& what) {
+        tr->err = std::string(fn) + ": " + what;
+        return MLD_ERR_INVALID_ARG;
+    };
+    if (!o.ids_out) return refuse("null ids_out table");
+    if (!o.offsets_out) return refuse("null offsets_out table");
+    if (!o.fp_out) return refuse("null fp_out table");
+    if (!o.spill_ids_out) return refuse("null spill_ids_out table");
+    if (!o.spill_fp_out) return refuse("null spill_fp_out table");
+    if (!o.track_capacity) return refuse("null track_capacity");
+    if (!o.entry_capacity) return refuse("null entry_capacity");
+    if (!o.spill_capacity) return refuse("null spill_capacity");
+    if (!o.record) return refuse("null record_out_dev");
+    if (mld_batch::misaligned(o.record, 7)) return refuse("record_out_dev is not 8-byte aligned");
+    for (int s = 0; s < tr->d.n_seq; s++) {
+        if (o.track_capacity[s] < 0) return refuse("negative track_capacity");
+        if (o.entry_capacity[s] < 0) return refuse("negative entry_capacity");
+        if (o.spill_capacity[s] < 0) return refuse("negative spill_capacity");
+        const bool has = every_sequence || tr->n_committed[(size_t)s] > 0;
+        if (has && o.track_capacity[s] > 0 && !o.ids_out[s]) return refuse("null ids_out array");
+        if (has && o.track_capacity[s] > 0 && !o.offsets_out[s]) return refuse("null offsets_out array");
+        if (has && o.entry_capacity[s] > 0 && !o.fp_out[s]) return refuse("null fp_out array");
+        if (has && o.spill_capacity[s] > 0 && !o.spill_ids_out[s]) return refuse("null spill_ids_out array");
+        if (has && o.spill_capacity[s] > 0 && !o.spill_fp_out[s]) return refuse("null spill_fp_out array");
+        if (mld_batch::misaligned(o.ids_out[s], 3)) return refuse("ids_out array is not 4-byte aligned");
+        if (mld_batch::misaligned(o.offsets_out[s], 7)) return refuse("offsets_out array is not 8-byte aligned");
+        if (mld_batch::misaligned(o.fp_out[s], 3)) return refuse("fp_out array is not 4-byte aligned");
+        if (mld_batch::misaligned(o.spill_ids_out[s], 3)) return refuse("spill_ids_out array is not 4-byte aligned");
+        if (mld_batch::misaligned(o.spill_fp_out[s], 3)) return refuse("spill_fp_out array is not 4-byte aligned");
+    }
+    return MLD_OK;
+}
+
+// The three launches of the leaving export behind the descriptor upload; mode[s] = kLeaveSkip / kLeaveMarks /
+// kLeaveFlush.  `o` has passed check_leaving.  A null array counts as capacity 0.
+int queue_leaving(mld_tracks* tr, const LeaveOut& o, const uint8_t* mode) {
+    const int S = tr->d.n_seq;
+    MLD_HIP(tr, hipSetDevice(tr->device));
+    for (int s = 0; s < S; s++) {
+        TrSeq& q = tr->ring.stage[(size_t)s];
+        q = TrSeq{};
+        q.leave_mode = mode[s];
+        if (mode[s] == kLeaveSkip) continue;
+        q.ids_out = o.ids_out[s];
+        q.offsets_out = o.offsets_out[s];
+        q.fp_out = o.fp_out[s];
+        q.spill_ids_out = o.spill_ids_out[s];
+        q.spill_fp_out = o.spill_fp_out[s];
+        q.track_capacity = q.ids_out && q.offsets_out ? o.track_capacity[s] : 0;
+        q.capacity = q.fp_out ? o.entry_capacity[s] : 0;
+        q.spill_capacity = q.spill_ids_out && q.spill_fp_out ? o.spill_capacity[s] : 0;
+        q.n = tr->n_committed[(size_t)s];
+    }
+    // (layout_blocks reads n_prev, which is leave_mode here: only its second total, which is not used, depends on it)
+    int64_t blocks = 0, blocks_prev = 0;
+    int rc = layout_blocks(tr, 1, &blocks, &blocks_prev);
+    if (rc) return rc;
+    if ((rc = tr->ring.upload(tr))) return rc;
+    if (blocks > 0) {
+        hipLaunchKernelGGL(k_tracks_leave_sums, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc,
+                           tr->committed, tr->epoch);
+        MLD_HIP(tr, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_tracks_leave_scan, dim3((unsigned)S), dim3(kScanWidth), 0, tr->stream, tr->d, tr->ring.d_desc,
+                       static_cast<long long*>(o.record));
+    MLD_HIP(tr, hipGetLastError());
+    if (blocks > 0) {
+        hipLaunchKernelGGL(k_tracks_leave_write, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc,
+                           tr->committed);
+        MLD_HIP(tr, hipGetLastError());
     }
     return MLD_OK;
 }
@@ -695,6 +973,7 @@ mld_tracks* mld_tracks_create(mld_ctx* ctx, int n_seq, int64_t max_tracks, int m
         tr->mask_pending.assign((size_t)n_seq, nullptr);
         tr->mask_table.assign((size_t)n_seq, nullptr);
         tr->lane_last.assign((size_t)n_seq, 0);
+        tr->leave_mode.assign((size_t)n_seq, 0);
         return allocate(tr);
     };
     return mld_batch::create_object<mld_tracks>(g_create_error, "mld_tracks_create", refusal(), ctx, status_out, init, free_own);
@@ -835,6 +1114,56 @@ int mld_tracks_export_packed_device(mld_tracks* tr, float* const* fp_out, const 
     MLD_HIP(tr, hipGetLastError());
     hipLaunchKernelGGL(k_tracks_pack_write, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed);
     MLD_HIP(tr, hipGetLastError());
+    return MLD_OK;
+}
+
+int mld_tracks_export_leaving_device(mld_tracks* tr, const uint8_t* flush, int32_t* const* ids_out, int64_t* const* offsets_out,
+                                     float* const* fp_out, int32_t* const* spill_ids_out, float* const* spill_fp_out,
+                                     const int64_t* track_capacity, const int64_t* entry_capacity, const int64_t* spill_capacity,
+                                     void* record_out_dev) {
+    if (!tr) return MLD_ERR_INVALID_ARG;
+    const LeaveOut o{ids_out, offsets_out, fp_out, spill_ids_out, spill_fp_out, track_capacity, entry_capacity, spill_capacity,
+                     record_out_dev};
+    int rc = check_leaving(tr, "mld_tracks_export_leaving_device", o, false);
+    if (rc) return rc;
+    const int S = tr->d.n_seq;
+    bool all_flushed = flush != nullptr;
+    for (int s = 0; s < S; s++) {
+        tr->leave_mode[(size_t)s] = flush && flush[s] ? kLeaveFlush : kLeaveMarks;
+        all_flushed = all_flushed && flush[s] != 0;
+    }
+    if (!tr->begun && !all_flushed)
+        return fail(tr, MLD_ERR_NOT_INITIALIZED,
+                    "mld_tracks_export_leaving_device without mld_tracks_begin_device (only a flush of every sequence needs none)");
+    return queue_leaving(tr, o, tr->leave_mode.data());
+}
+
+int mld_tracks_set_leaving_sink(mld_tracks* tr, int32_t* const* ids_out, int64_t* const* offsets_out, float* const* fp_out,
+                                int32_t* const* spill_ids_out, float* const* spill_fp_out, const int64_t* track_capacity,
+                                const int64_t* entry_capacity, const int64_t* spill_capacity, void* record_out_dev) {
+    if (!tr) return MLD_ERR_INVALID_ARG;
+    if (!ids_out && !offsets_out && !fp_out && !spill_ids_out && !spill_fp_out && !track_capacity && !entry_capacity &&
+        !spill_capacity && !record_out_dev) {  // (all null: the sink is taken away)
+        tr->sink_armed = false;
+        return MLD_OK;
+    }
+    const LeaveOut o{ids_out, offsets_out, fp_out, spill_ids_out, spill_fp_out, track_capacity, entry_capacity, spill_capacity,
+                     record_out_dev};
+    const int rc = check_leaving(tr, "mld_tracks_set_leaving_sink", o, true);
+    if (rc) return rc;  // (a sink armed before stays as it was)
+    const size_t S = (size_t)tr->d.n_seq;
+    tr->sink_ids.assign(ids_out, ids_out + S);
+    tr->sink_offsets.assign(offsets_out, offsets_out + S);
+    tr->sink_fp.assign(fp_out, fp_out + S);
+    tr->sink_spill_ids.assign(spill_ids_out, spill_ids_out + S);
+    tr->sink_spill_fp.assign(spill_fp_out, spill_fp_out + S);
+    tr->sink_caps.assign(track_capacity, track_capacity + S);
+    tr->sink_caps.insert(tr->sink_caps.end(), entry_capacity, entry_capacity + S);
+    tr->sink_caps.insert(tr->sink_caps.end(), spill_capacity, spill_capacity + S);
+    tr->sink = LeaveOut{tr->sink_ids.data(), tr->sink_offsets.data(), tr->sink_fp.data(), tr->sink_spill_ids.data(),
+                        tr->sink_spill_fp.data(), tr->sink_caps.data(), tr->sink_caps.data() + S, tr->sink_caps.data() + 2 * S,
+                        record_out_dev};
+    tr->sink_armed = true;
     return MLD_OK;
 }
 
@@ -1000,11 +1329,25 @@ static int tracklets_step(const char* fn, mld_ctx* ctx, mld_tracks* tr, int bank
     int rc;
     bool any_restart = false;
     for (int s = 0; restart && s < S; s++) any_restart = any_restart || restart[s] != 0;
-    if (any_restart) {  // (what the begin would refuse is refused before a lane is emptied)
+    // A sink (mld_tracks_set_leaving_sink) takes what this step removes from the store, every sequence in exactly one
+    // of two passes: the restarting ones whole, before they are emptied; the others by the marks of this step's look-up.
+    const bool sink = tr->sink_armed;
+    if (any_restart || sink) {  // (what the begin would refuse is refused before a lane is emptied or the sink written)
         if ((rc = check_begin(tr, fn, ids, n_tracks, nullptr))) return rc;
+    }
+    if (any_restart) {
+        if (sink) {
+            for (int s = 0; s < S; s++) tr->leave_mode[(size_t)s] = restart[s] ? kLeaveFlush : kLeaveSkip;
+            if ((rc = queue_leaving(tr, tr->sink, tr->leave_mode.data()))) return rc;
+        }
         if ((rc = import_packed(tr, fn, restart, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
     }
     if ((rc = mld_tracks_begin_device(tr, ids, n_tracks, nullptr))) return rc;
+    if (sink) {
+        for (int s = 0; s < S; s++) tr->leave_mode[(size_t)s] = any_restart && restart[s] ? kLeaveSkip : kLeaveMarks;
+        tr->sink_armed = false;  // one step, whatever becomes of it from here on
+        if ((rc = queue_leaving(tr, tr->sink, tr->leave_mode.data()))) return rc;
+    }
     for (int s = 0; s < S; s++) tr->mask_table[(size_t)s] = tr->mask_pending[(size_t)s];
     int with = 0;
     for (int s = 0; have_last && s < S; s++) {

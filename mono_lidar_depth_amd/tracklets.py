@@ -230,7 +230,8 @@ class TrackletStore(_BatchObject):
     """`_trackletMap` of S independent sequences in GPU memory (mld_tracks_*, include/mld.h): begin = which ids are new
     (ExractNewTrackletFrames :23-61), commit = SaveFeatureDepths + TidyUpTracklets (:119-193), export =
     convert_tracklets_to_matches_msg (:209-259).  Histories hold at most `max_history` entries per track (the
-    reference's deque is unbounded).  Lists of S torch CUDA tensors in and out; asynchronous on the estimator's stream,
+    reference's deque is unbounded; export_leaving() hands out what falls off and the tracks that end, TrackArchive
+    puts them together).  Lists of S torch CUDA tensors in and out; asynchronous on the estimator's stream,
     only counts() synchronises.  Close the store before its estimator."""
 
     COUNT_NAMES = ("live", "new", "old", "features_ok", "features_failed", "duplicates")
@@ -286,6 +287,98 @@ class TrackletStore(_BatchObject):
         self._check(self._lib.mld_tracks_export_packed_device(self._tr, self._vp(fp_out), cap, self._vp(offsets_out)))
         self._hold((list(fp_out) if fp_out is not None else None, list(offsets_out) if offsets_out is not None else None),
                    "export_packed")
+
+    LEAVING_KEYS = ("ids", "offsets", "fp", "spill_ids", "spill_fp")
+
+    def leaving_buffers(self, n_tracks, device=None) -> dict:
+        """Output tensors of export_leaving() / set_leaving_sink() that never truncate sequences whose last committed
+        frame holds n_tracks[s] tracks: {"ids", "offsets", "fp", "spill_ids", "spill_fp"} (lists of S) and "record"."""
+        import torch
+        dev = device if device is not None else torch.device("cuda", self._est._device)
+        ns = [int(n) for n in n_tracks]
+        if len(ns) != self.S:
+            raise ValueError(f"n_tracks: expected {self.S} counts, one per sequence")
+        mk = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+        return {"ids": [mk((n,), torch.int32) for n in ns], "offsets": [mk((n + 1,), torch.int64) for n in ns],
+                "fp": [mk((n * self.max_history, 3), torch.float32) for n in ns],
+                "spill_ids": [mk((n,), torch.int32) for n in ns], "spill_fp": [mk((n, 3), torch.float32) for n in ns],
+                "record": mk((self.S, 4), torch.int64)}
+
+    def _leaving_args(self, ids, offsets, fp, spill_ids, spill_fp, record):
+        """(pointer tables, capacity tables, record pointer, what to keep alive) from lists of S tensors (an entry None:
+        capacity 0).  The capacities are the tensors' sizes: ids [t], offsets [>= t + 1], fp [e, 3], spill_ids [p],
+        spill_fp [>= p, 3]."""
+        S = self.S
+        lists = (ids, offsets, fp, spill_ids, spill_fp)
+        for name, ts in zip(self.LEAVING_KEYS, lists):
+            if len(ts) != S:
+                raise ValueError(f"{name}: expected {S} entries, one per sequence")
+            for t in ts:
+                if t is not None and not t.is_contiguous():
+                    raise ValueError(f"{name}: contiguous tensors")
+        if record.element_size() != 8 or int(record.numel()) < 4 * S or not record.is_contiguous():
+            raise ValueError(f"record: a contiguous int64 tensor [{S}, 4]")
+        size = lambda t, per=1: int(t.numel()) // per if t is not None else 0  # noqa: E731
+        tcap, ecap, scap = [], [], []
+        for s in range(S):
+            t = size(ids[s])
+            if t and size(offsets[s]) < t + 1:
+                raise ValueError(f"sequence {s}: offsets must hold one more entry than ids")
+            p = size(spill_ids[s])
+            if p and size(spill_fp[s], 3) < p:
+                raise ValueError(f"sequence {s}: spill_fp must hold 3 floats per entry of spill_ids")
+            tcap.append(t)
+            ecap.append(size(fp[s], 3))
+            scap.append(p)
+        i64 = lambda v: (C.c_int64 * S)(*v)  # noqa: E731
+        args = [self._ptrs(ts) for ts in lists] + [i64(tcap), i64(ecap), i64(scap), C.c_void_p(int(record.data_ptr()))]
+        return args, ([list(ts) for ts in lists], record)
+
+    def export_leaving(self, ids, offsets, fp, spill_ids, spill_fp, record, flush=None):
+        """What the commit of the begun frame removes from the store (mld_tracks_export_leaving_device), between begin()
+        and commit(): per sequence the tracks that end - ids [t] int32, offsets [t + 1] int64 and entries [e, 3] float32
+        as export_packed() lays them out - and, for every continuing track with max_history entries, the id and the
+        oldest entry that commit() overwrites (spill_ids [p], spill_fp [p, 3]).  Lists of S CUDA tensors (an entry None:
+        capacity 0) whose sizes are the capacities; record: an int64 CUDA tensor [S, 4] that receives (n_ended,
+        n_ended_entries, n_spilled, 0) complete, so that a count above a capacity tells a truncated sequence.
+        leaving_buffers() makes a set that never truncates.  flush: None, or S flags - a flagged sequence gives all its
+        tracks as ended and spills nothing; with every flag set no begun frame is needed."""
+        args, keep = self._leaving_args(ids, offsets, fp, spill_ids, spill_fp, record)
+        self._check(self._lib.mld_tracks_export_leaving_device(self._tr, self._select(flush), *args))
+        self._hold(keep, "export_leaving")
+
+    def set_leaving_sink(self, ids=None, offsets=None, fp=None, spill_ids=None, spill_fp=None, record=None):
+        """The outputs of export_leaving() for the NEXT TrackletBatch.step() on this store
+        (mld_tracks_set_leaving_sink): restarting lanes are flushed into them before they are emptied, the other lanes
+        exported after the step's look-up.  One step consumes the sink.  Without arguments: the sink is taken away."""
+        if all(a is None for a in (ids, offsets, fp, spill_ids, spill_fp, record)):
+            self._check(self._lib.mld_tracks_set_leaving_sink(self._tr, *([None] * 9)))
+            self._keep.pop("leaving_sink", None)
+            return
+        args, keep = self._leaving_args(ids, offsets, fp, spill_ids, spill_fp, record)
+        self._check(self._lib.mld_tracks_set_leaving_sink(self._tr, *args))
+        self._hold(keep, "leaving_sink")
+
+    @classmethod
+    def leaving_host(cls, buf) -> list:
+        """The buffers of a finished export_leaving() on the host, per sequence {"ids", "offsets", "fp", "spill_ids",
+        "spill_fp", "record"} trimmed to what was written - what TrackArchive.push() takes.  The caller has
+        synchronised."""
+        rec = buf["record"].cpu().numpy().reshape(-1, 4)
+        out = []
+        for s in range(rec.shape[0]):
+            host = {k: (buf[k][s].cpu().numpy() if buf[k][s] is not None else None) for k in cls.LEAVING_KEYS}
+            size = lambda k, per=1: host[k].size // per if host[k] is not None else 0  # noqa: E731
+            t = min(int(rec[s, 0]), size("ids"))
+            e = min(int(rec[s, 1]), size("fp", 3))
+            p = min(int(rec[s, 2]), size("spill_ids"))
+            out.append({"ids": host["ids"][:t] if t else np.zeros(0, np.int32),
+                        "offsets": host["offsets"][:t + 1] if t else np.zeros(1, np.int64),
+                        "fp": host["fp"].reshape(-1, 3)[:e] if e else np.zeros((0, 3), np.float32),
+                        "spill_ids": host["spill_ids"][:p] if p else np.zeros(0, np.int32),
+                        "spill_fp": host["spill_fp"].reshape(-1, 3)[:p] if p else np.zeros((0, 3), np.float32),
+                        "record": rec[s].copy()})
+        return out
 
     def _select(self, select):
         if select is None:
@@ -1291,16 +1384,21 @@ class TrackletBatch:
                 "features": (list(u_new), list(v_new)),
                 "current": (list(d_cur), list(t_cur) if t_cur is not None else None)}
 
-    def step(self, f, nxt: Optional["TrackletBatch"] = None, handover: str = "projection", restart=None):
+    def step(self, f, nxt: Optional["TrackletBatch"] = None, handover: str = "projection", restart=None, leaving=None):
         """run() with the tracklet maps on the GPU (mld_tracklets_step_device): projection of the current bank, then
         new-track decision -> depths -> histories as one asynchronous chain.  `f` from prepare_step(); attach_store()
         first.  The histories are read with store.export(...).  restart: None, or S flags - a lane with a flag starts a
         new recording on this frame: its store is emptied first, every id of it is new and its d_last is -1.  With lanes
-        that differ (restart, or lane_has_last) the call is mld_tracklets_step_lanes_device, else today's."""
+        that differ (restart, or lane_has_last) the call is mld_tracklets_step_lanes_device, else today's.
+        leaving: None, or the buffers of store.set_leaving_sink() as a dict (store.leaving_buffers() makes one) - they
+        receive what this step removes from the store: a restarting lane's tracks whole, of the other lanes the tracks
+        that end and the entries that fall off (store.export_leaving)."""
         if self.store is None:
             raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.step without attach_store")
         S, est, lib = self.S, self.est, self.est._lib
         uniform, last, again = self._lane_flags(restart)
+        if leaving is not None:
+            self.store.set_leaving_sink(**{k: leaving[k] for k in TrackletStore.LEAVING_KEYS + ("record",)})
         self._project(f, last)
         if nxt is not None and nxt is not self:
             if handover == "classify":
