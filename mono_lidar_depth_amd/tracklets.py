@@ -169,12 +169,109 @@ class TrackletDepthModule:
         return list(self._tracklet_map[track_id])
 
 
+def mask_words(n_points: int) -> int:
+    """32-bit words of the inlier mask of a cloud of n_points."""
+    return (int(n_points) + 31) // 32
+
+
+def _at(ts, s):
+    """Entry s of a table that may be absent."""
+    return ts[s] if ts is not None else None
+
+
+def _entries(t, per: int = 1) -> int:
+    """Whole groups of `per` elements a tensor holds (None: 0)."""
+    return int(t.numel()) // per if t is not None else 0
+
+
+def _holds(t, s, entries, size, name, required=False):
+    """Tensor `t` of sequence s is contiguous, of `size`-byte elements and at least `entries` long.  None passes,
+    unless `required` and entries > 0."""
+    if t is None:
+        if required and entries:
+            raise ValueError(f"sequence {s}: {name} is missing")
+        return
+    if t.element_size() != size or not t.is_contiguous() or int(t.numel()) < entries:
+        raise ValueError(f"sequence {s}: {name} must be contiguous, of {size}-byte elements, at least {entries} of them")
+
+
+def _mask_room(t, s, n_points, name):
+    """Tensor `t` has room for the inlier mask of n_points, counted in bytes whatever its element type."""
+    if t is None or int(t.numel()) * t.element_size() < 4 * mask_words(n_points):
+        raise ValueError(f"sequence {s}: {name} holds fewer than {mask_words(n_points)} words")
+
+
+def _cloud_table(clouds, none_allowed=True):
+    """(width, ns) of the clouds of a call: contiguous float32 [n, 4] or [n, 8] of one width.  An entry None is a
+    sequence without points where `none_allowed`, else refused."""
+    width = next((int(cl.shape[1]) for cl in clouds if cl is not None and cl.dim() == 2), 4)
+    ns = []
+    for s, cl in enumerate(clouds):
+        if cl is None and not none_allowed:
+            raise ValueError(f"sequence {s}: clouds is missing")
+        if cl is not None and (cl.dim() != 2 or int(cl.shape[1]) != width or width not in (4, 8) or not cl.is_contiguous()
+                               or cl.element_size() != 4):
+            raise ValueError("clouds: contiguous float32 [n, 4] or [n, 8], one width for all sequences")
+        ns.append(int(cl.shape[0]) if cl is not None else 0)
+    return width, ns
+
+
+def _capacities(capacity, ns, clamp=False):
+    """The capacity of every sequence: capacity[s], or ns[s] without a table; a negative one is refused.  clamp: at most
+    ns[s] - what TrackletBatch allocates."""
+    caps = []
+    for s, n in enumerate(ns):
+        cap = n if capacity is None else int(capacity[s])
+        if cap < 0:
+            raise ValueError(f"sequence {s}: negative capacity")
+        caps.append(min(cap, n) if clamp else cap)
+    return caps
+
+
+def _result_tensor(t, shape, size, name):
+    """Tensor `t`, which receives the records of a call, is contiguous, of exactly `shape` and of `size`-byte elements."""
+    if tuple(t.shape) != tuple(shape) or t.element_size() != size or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous int{8 * size} tensor {list(shape)}")
+
+
 class _BatchObject:
-    """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes, ProjectedClouds, DepthReports, PlaneInliers, FeatureTraces and CoverageMaps share: an object of the C-ABI (mld_<_NAME>_create /
-    _destroy / _last_error) on an estimator's context, its handle in the attribute named _HANDLE, and the tensors of
-    the calls that may still be queued."""
+    """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes, ProjectedClouds, DepthReports, PlaneInliers,
+    FeatureTraces and CoverageMaps share: an object of the C-ABI (mld_<_NAME>_create / _destroy / _last_error) on an
+    estimator's context, its handle in the attribute named _HANDLE, the tensors of the calls that may still be queued,
+    and one copy of every argument check.  The helpers, here and above:
+
+    _calibration     the parameter, camera and transform arguments of _create
+    _create, close   the object of the C-ABI; _check raises its last error for a status that is not MLD_OK
+    _lengths         every list given holds one entry per sequence
+    _ptrs, _opt      the pointer table of S tensors; _opt: NULL for a table that is absent
+    _i64             a table of S int64 (None: NULL)
+    _plane_args      plane coefficients and masks, which come together or not at all
+    _image_geometry  (rows, cols, row stride) the label images share
+    _hold            keeps the tensors of a call alive for two calls
+    _holds           a tensor is contiguous, of the element size and long enough; _mask_room: for a mask, in bytes
+    _cloud_table     (width, ns) of the clouds
+    _capacities      the capacity table, as given or clamped to the clouds
+    _result_tensor   the fixed shape of a tensor that receives records
+    _at, _entries    an entry of an optional table; the entries of an optional tensor
+    mask_words       words of an inlier mask"""
 
     _NAME = _HANDLE = ""
+
+    def _calibration(self, estimator: DepthEstimator, *parts, parameters=None):
+        """The arguments of _create named in `parts`, in that order: "parameters" (the given ones, else the estimator's),
+        "camera" (also sets self.width and self.height), "transform" (its first 12 doubles).  Each keeps its object alive."""
+        out = []
+        for part in parts:
+            if part == "parameters":
+                out.append(C.byref(parameters if parameters is not None else estimator.getParameters()))
+            elif part == "camera":
+                cam = estimator._camera.as_struct()
+                self.width, self.height = int(cam.width), int(cam.height)
+                out.append(C.byref(cam))
+            else:
+                T = np.ascontiguousarray(np.asarray(estimator._T, dtype=np.float64).reshape(-1)[:12])
+                out.append(T.ctypes.data_as(C.POINTER(C.c_double)))
+        return out
 
     def _create(self, estimator: DepthEstimator, *args):
         self._est, self._lib = estimator, estimator._lib
@@ -192,14 +289,38 @@ class _BatchObject:
         if rc != capi.MLD_OK:
             raise DepthEstimatorError(rc, self._last_error(getattr(self, self._HANDLE)))
 
+    def _lengths(self, **lists):
+        """Every list given holds one entry per sequence (None: the list is absent and not looked at)."""
+        for name, ts in lists.items():
+            if ts is not None and len(ts) != self.S:
+                raise ValueError(f"{name}: expected {self.S} entries, one per sequence")
+
     def _ptrs(self, ts):
         """The table of the S device pointers of `ts` (an entry None: NULL)."""
         return (C.c_void_p * self.S)(*[int(t.data_ptr()) if t is not None else None for t in ts])
 
-    def _hold(self, now, call=None):
-        """The arrays must outlive the asynchronous launches (the previous call's as well: it may still be queued)."""
+    def _opt(self, ts):
+        """_ptrs of a table that may be absent (None: NULL)."""
+        return self._ptrs(ts) if ts is not None else None
+
+    def _i64(self, values):
+        """The table of S int64 `values` (None: NULL)."""
+        return (C.c_int64 * self.S)(*values) if values is not None else None
+
+    def _plane_args(self, coeffs, masks):
+        """(pointer to the float32 [S, 4] coefficients, mask table) of the planes of a call: both or neither."""
+        if (coeffs is None) != (masks is None):
+            raise ValueError("coeffs and masks come together or not at all")
+        if coeffs is None:
+            return None, None
+        co = np.ascontiguousarray(coeffs, dtype=np.float32).reshape(self.S, 4)
+        return co.ctypes.data_as(C.POINTER(C.c_float)), self._ptrs(masks)
+
+    def _hold(self, *now, call=None):
+        """The arrays must outlive the asynchronous launches (the previous call's as well: it may still be queued).
+        `now`: tensors, lists of tensors and Nones as the call took them."""
         prev = self._keep.get(call)
-        self._keep[call] = (prev[1] if prev else None, now)
+        self._keep[call] = (prev[1] if prev else None, [list(x) if isinstance(x, (list, tuple)) else x for x in now])
 
     @staticmethod
     def _image_geometry(images):
@@ -241,32 +362,28 @@ class TrackletStore(_BatchObject):
         self.S, self.max_tracks, self.max_history = int(n_seq), int(max_tracks), int(max_history)
         self._create(estimator, self.S, self.max_tracks, self.max_history)
 
-    def _vp(self, ts):
-        if ts is None:
-            return None
-        if len(ts) != self.S:
-            raise ValueError(f"expected {self.S} tensors, one per sequence")
-        return self._ptrs(ts)
-
     def begin(self, ids, is_new_out=None):
         """ids: S int32 CUDA tensors; is_new_out: S uint8 CUDA tensors of the same lengths, or None (masks kept in
         the store).  The ids are read again by commit()."""
-        self._check(self._lib.mld_tracks_begin_device(self._tr, self._vp(ids), (C.c_int64 * self.S)(*[int(t.shape[0]) for t in ids]),
-                                                      self._vp(is_new_out)))
-        self._keep["begin"] = (list(ids), list(is_new_out) if is_new_out is not None else None)
+        self._lengths(ids=ids, is_new_out=is_new_out)
+        self._check(self._lib.mld_tracks_begin_device(self._tr, self._opt(ids), self._i64(int(t.shape[0]) for t in ids),
+                                                      self._opt(is_new_out)))
+        self._hold(ids, is_new_out, call="begin")
 
     def commit(self, u_new, v_new, u_old, v_old, d_cur, d_last):
         """S float32 CUDA tensors each, indexed as the ids of begin(); d_cur / d_last: the depths of
         mld_tracklets_depths_device (d_last is read where the track is new)."""
         arrs = (u_new, v_new, u_old, v_old, d_cur, d_last)
-        self._check(self._lib.mld_tracks_commit_device(self._tr, *[self._vp(a) for a in arrs]))
-        self._keep["commit"] = [list(a) for a in arrs]
+        self._lengths(u_new=u_new, v_new=v_new, u_old=u_old, v_old=v_old, d_cur=d_cur, d_last=d_last)
+        self._check(self._lib.mld_tracks_commit_device(self._tr, *[self._opt(a) for a in arrs]))
+        self._hold(*arrs, call="commit")
 
     def export(self, fp_out, len_out):
         """fp_out: S float32 CUDA tensors [n_tracks, max_history, 3] ((u, v, d), newest first; rows beyond a track's
         length stay untouched), len_out: S int32 CUDA tensors [n_tracks]; the tracks of the last committed frame."""
-        self._check(self._lib.mld_tracks_export_device(self._tr, self._vp(fp_out), self._vp(len_out)))
-        self._keep["export"] = (fp_out, len_out)
+        self._lengths(fp_out=fp_out, len_out=len_out)
+        self._check(self._lib.mld_tracks_export_device(self._tr, self._opt(fp_out), self._opt(len_out)))
+        self._hold(fp_out, len_out, call="export")
 
     def packed_capacity(self, n_tracks: int) -> int:
         """Entries an fp_out of export_packed() needs so that a sequence of n_tracks tracks is never truncated."""
@@ -278,15 +395,15 @@ class TrackletStore(_BatchObject):
         sequence's total.  fp_out: None (offsets only), or S contiguous float32 CUDA tensors [capacity, 3] ((u, v, d),
         newest first within a track); entries at or beyond a tensor's capacity are dropped, which the caller sees from
         offsets[n_tracks] > capacity.  packed_capacity(n_tracks) never truncates."""
+        self._lengths(fp_out=fp_out, offsets_out=offsets_out)
         cap = None
         if fp_out is not None:
             for t in fp_out:
                 if not t.is_contiguous():
                     raise ValueError("fp_out: contiguous tensors")
-            cap = (C.c_int64 * self.S)(*[int(t.numel()) // 3 for t in fp_out])
-        self._check(self._lib.mld_tracks_export_packed_device(self._tr, self._vp(fp_out), cap, self._vp(offsets_out)))
-        self._hold((list(fp_out) if fp_out is not None else None, list(offsets_out) if offsets_out is not None else None),
-                   "export_packed")
+            cap = [_entries(t, 3) for t in fp_out]
+        self._check(self._lib.mld_tracks_export_packed_device(self._tr, self._opt(fp_out), self._i64(cap), self._opt(offsets_out)))
+        self._hold(fp_out, offsets_out, call="export_packed")
 
     LEAVING_KEYS = ("ids", "offsets", "fp", "spill_ids", "spill_fp")
 
@@ -296,8 +413,7 @@ class TrackletStore(_BatchObject):
         import torch
         dev = device if device is not None else torch.device("cuda", self._est._device)
         ns = [int(n) for n in n_tracks]
-        if len(ns) != self.S:
-            raise ValueError(f"n_tracks: expected {self.S} counts, one per sequence")
+        self._lengths(n_tracks=ns)
         mk = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
         return {"ids": [mk((n,), torch.int32) for n in ns], "offsets": [mk((n + 1,), torch.int64) for n in ns],
                 "fp": [mk((n * self.max_history, 3), torch.float32) for n in ns],
@@ -305,34 +421,31 @@ class TrackletStore(_BatchObject):
                 "record": mk((self.S, 4), torch.int64)}
 
     def _leaving_args(self, ids, offsets, fp, spill_ids, spill_fp, record):
-        """(pointer tables, capacity tables, record pointer, what to keep alive) from lists of S tensors (an entry None:
-        capacity 0).  The capacities are the tensors' sizes: ids [t], offsets [>= t + 1], fp [e, 3], spill_ids [p],
+        """(pointer tables, capacity tables and record pointer, what to keep alive) from lists of S tensors (an entry
+        None: capacity 0).  The capacities are the tensors' sizes: ids [t], offsets [>= t + 1], fp [e, 3], spill_ids [p],
         spill_fp [>= p, 3]."""
         S = self.S
         lists = (ids, offsets, fp, spill_ids, spill_fp)
+        self._lengths(**dict(zip(self.LEAVING_KEYS, lists)))
         for name, ts in zip(self.LEAVING_KEYS, lists):
-            if len(ts) != S:
-                raise ValueError(f"{name}: expected {S} entries, one per sequence")
             for t in ts:
                 if t is not None and not t.is_contiguous():
                     raise ValueError(f"{name}: contiguous tensors")
-        if record.element_size() != 8 or int(record.numel()) < 4 * S or not record.is_contiguous():
-            raise ValueError(f"record: a contiguous int64 tensor [{S}, 4]")
-        size = lambda t, per=1: int(t.numel()) // per if t is not None else 0  # noqa: E731
+        _holds(record, "*", 4 * S, 8, "record", required=True)
         tcap, ecap, scap = [], [], []
         for s in range(S):
-            t = size(ids[s])
-            if t and size(offsets[s]) < t + 1:
+            t = _entries(ids[s])
+            if t and _entries(offsets[s]) < t + 1:
                 raise ValueError(f"sequence {s}: offsets must hold one more entry than ids")
-            p = size(spill_ids[s])
-            if p and size(spill_fp[s], 3) < p:
+            p = _entries(spill_ids[s])
+            if p and _entries(spill_fp[s], 3) < p:
                 raise ValueError(f"sequence {s}: spill_fp must hold 3 floats per entry of spill_ids")
             tcap.append(t)
-            ecap.append(size(fp[s], 3))
+            ecap.append(_entries(fp[s], 3))
             scap.append(p)
-        i64 = lambda v: (C.c_int64 * S)(*v)  # noqa: E731
-        args = [self._ptrs(ts) for ts in lists] + [i64(tcap), i64(ecap), i64(scap), C.c_void_p(int(record.data_ptr()))]
-        return args, ([list(ts) for ts in lists], record)
+        args = [self._ptrs(ts) for ts in lists] + [self._i64(tcap), self._i64(ecap), self._i64(scap),
+                                                   C.c_void_p(int(record.data_ptr()))]
+        return args, lists + (record,)
 
     def export_leaving(self, ids, offsets, fp, spill_ids, spill_fp, record, flush=None):
         """What the commit of the begun frame removes from the store (mld_tracks_export_leaving_device), between begin()
@@ -345,7 +458,7 @@ class TrackletStore(_BatchObject):
         tracks as ended and spills nothing; with every flag set no begun frame is needed."""
         args, keep = self._leaving_args(ids, offsets, fp, spill_ids, spill_fp, record)
         self._check(self._lib.mld_tracks_export_leaving_device(self._tr, self._select(flush), *args))
-        self._hold(keep, "export_leaving")
+        self._hold(*keep, call="export_leaving")
 
     def set_leaving_sink(self, ids=None, offsets=None, fp=None, spill_ids=None, spill_fp=None, record=None):
         """The outputs of export_leaving() for the NEXT TrackletBatch.step() on this store
@@ -357,7 +470,7 @@ class TrackletStore(_BatchObject):
             return
         args, keep = self._leaving_args(ids, offsets, fp, spill_ids, spill_fp, record)
         self._check(self._lib.mld_tracks_set_leaving_sink(self._tr, *args))
-        self._hold(keep, "leaving_sink")
+        self._hold(*keep, call="leaving_sink")
 
     @classmethod
     def leaving_host(cls, buf) -> list:
@@ -381,11 +494,9 @@ class TrackletStore(_BatchObject):
         return out
 
     def _select(self, select):
-        if select is None:
-            return None
-        if len(select) != self.S:
-            raise ValueError(f"select: expected {self.S} flags, one per sequence")
-        return (C.c_uint8 * self.S)(*[1 if x else 0 for x in select])
+        """The table of S flags (None: NULL, which selects all)."""
+        self._lengths(select=select)
+        return (C.c_uint8 * self.S)(*[1 if x else 0 for x in select]) if select is not None else None
 
     def import_packed(self, ids, offsets, fp, select=None):
         """The inverse of export_packed() (mld_tracks_import_packed_device): the committed frame of every selected
@@ -395,26 +506,22 @@ class TrackletStore(_BatchObject):
         select: None (all), or S flags; the entries of a sequence that is not selected may be None and the sequence is
         not touched.  A selected sequence whose ids is None or empty is emptied.  Histories longer than max_history keep
         their newest entries; offsets are clamped to the entries fp holds.  A begun frame is abandoned."""
-        S = self.S
-        for name, ts in (("ids", ids), ("offsets", offsets), ("fp", fp)):
-            if len(ts) != S:
-                raise ValueError(f"{name}: expected {S} entries, one per sequence")
+        self._lengths(ids=ids, offsets=offsets, fp=fp, select=select)
         nt, ne = [], []
-        for s in range(S):
+        for s in range(self.S):
             on = select is None or bool(select[s])
             n = int(ids[s].shape[0]) if on and ids[s] is not None else 0
             if n:
-                if offsets[s] is None or int(offsets[s].numel()) != n + 1 or offsets[s].element_size() != 8 or not offsets[s].is_contiguous():
-                    raise ValueError(f"sequence {s}: offsets must be a contiguous int64 tensor of {n + 1} entries")
-                if fp[s] is not None and (fp[s].element_size() != 4 or not fp[s].is_contiguous()):
-                    raise ValueError(f"sequence {s}: fp must be a contiguous float32 tensor")
+                _holds(offsets[s], s, n + 1, 8, "offsets", required=True)
+                if int(offsets[s].numel()) != n + 1:
+                    raise ValueError(f"sequence {s}: offsets must hold {n + 1} entries")
+                _holds(fp[s], s, 0, 4, "fp")
             nt.append(n)
-            ne.append(int(fp[s].numel()) // 3 if n and fp[s] is not None else 0)
-        live = lambda ts: [t if nt[s] else None for s, t in enumerate(ts)]  # noqa: E731
-        self._check(self._lib.mld_tracks_import_packed_device(self._tr, self._select(select), self._ptrs(live(ids)),
-                                                              (C.c_int64 * S)(*nt), self._ptrs(live(offsets)),
-                                                              self._ptrs(live(fp)), (C.c_int64 * S)(*ne)))
-        self._hold((live(ids), live(offsets), live(fp)), "import_packed")
+            ne.append(_entries(fp[s], 3) if n else 0)
+        ids, offsets, fp = ([t if nt[s] else None for s, t in enumerate(ts)] for ts in (ids, offsets, fp))
+        self._check(self._lib.mld_tracks_import_packed_device(self._tr, self._select(select), self._ptrs(ids), self._i64(nt),
+                                                              self._ptrs(offsets), self._ptrs(fp), self._i64(ne)))
+        self._hold(ids, offsets, fp, call="import_packed")
 
     def reset(self, select=None):
         """Empties the selected sequences (None: all) - import_packed() of no tracks (mld_tracks_reset_device)."""
@@ -444,22 +551,19 @@ class SemanticLabels(_BatchObject):
         height); u, v: S float32 CUDA tensors, the newest feature of every track; label_out: S int16 CUDA tensors of
         the same lengths; votes_out: None, or S int32 CUDA tensors [n, 2] (single entries may be None) that receive
         (count of the winning label, pixels in the clipped window)."""
-        S = self.S
-        for name, ts in (("images", images), ("u", u), ("v", v), ("label_out", label_out), ("votes_out", votes_out)):
-            if ts is not None and len(ts) != S:
-                raise ValueError(f"{name}: expected {S} tensors, one per sequence")
+        self._lengths(images=images, u=u, v=v, label_out=label_out, votes_out=votes_out)
         rows, cols, stride = self._image_geometry(images)
-        for s in range(S):
+        for s in range(self.S):
             n = int(u[s].shape[0])
             if int(v[s].shape[0]) != n or int(label_out[s].shape[0]) != n:
                 raise ValueError(f"sequence {s}: u, v and label_out differ in length")
-            if votes_out is not None and votes_out[s] is not None and tuple(votes_out[s].shape) != (n, 2):
+            if _at(votes_out, s) is not None and tuple(votes_out[s].shape) != (n, 2):
                 raise ValueError(f"sequence {s}: votes_out must be [{n}, 2]")
         vp = self._ptrs
         self._check(self._lib.mld_labels_assign_device(
             self._lb, vp(images), rows, cols, max(stride, cols), int(roi[0]), int(roi[1]), vp(u), vp(v),
-            (C.c_int64 * S)(*[int(t.shape[0]) for t in u]), vp(label_out), vp(votes_out) if votes_out is not None else None))
-        self._hold((list(images), list(u), list(v), list(label_out), list(votes_out) if votes_out is not None else None))
+            self._i64(int(t.shape[0]) for t in u), vp(label_out), self._opt(votes_out)))
+        self._hold(images, u, v, label_out, votes_out)
 
 
 class SemanticPlanes(_BatchObject):
@@ -470,42 +574,29 @@ class SemanticPlanes(_BatchObject):
     the estimator's stream.  Close it before its estimator."""
 
     _NAME, _HANDLE = "semantic_planes", "_sp"
+    mask_words = staticmethod(mask_words)
 
     def __init__(self, estimator: DepthEstimator, n_seq: int, max_points: int):
         self.S, self.max_points = int(n_seq), int(max_points)
-        cam = estimator._camera.as_struct()
-        T = np.ascontiguousarray(np.asarray(estimator._T, dtype=np.float64).reshape(-1)[:12])
-        self._create(estimator, self.S, self.max_points, C.byref(cam), T.ctypes.data_as(C.POINTER(C.c_double)))
-
-    @staticmethod
-    def mask_words(n_points: int) -> int:
-        """32-bit words of the inlier mask of a cloud of n_points."""
-        return (int(n_points) + 31) // 32
+        self._create(estimator, self.S, self.max_points, *self._calibration(estimator, "camera", "transform"))
 
     def estimate(self, clouds, images, labels, inlier_threshold: float, result_out, masks_out):
         """clouds: S contiguous float32 CUDA tensors [n, 4] or [n, 8] of one width; images: S uint8 CUDA tensors
         [rows, cols] of one shape and row stride (unit column stride); labels: the ground labels; result_out: an int32
         CUDA tensor [S, 8] that receives the records (capi.MldSemanticPlaneResult: coefficients as float bits, then
         n_candidates, n_inliers, status, 0); masks_out: S int32 CUDA tensors of at least mask_words(n) entries."""
-        S = self.S
-        for name, ts in (("clouds", clouds), ("images", images), ("masks_out", masks_out)):
-            if len(ts) != S:
-                raise ValueError(f"{name}: expected {S} tensors, one per sequence")
-        width = int(clouds[0].shape[1])
-        for s, cl in enumerate(clouds):
-            if cl.dim() != 2 or int(cl.shape[1]) != width or width not in (4, 8) or not cl.is_contiguous() or cl.element_size() != 4:
-                raise ValueError("clouds: contiguous float32 [n, 4] or [n, 8], one width for all sequences")
-            if int(masks_out[s].numel()) * masks_out[s].element_size() < 4 * self.mask_words(cl.shape[0]):
-                raise ValueError(f"sequence {s}: masks_out holds fewer than {self.mask_words(cl.shape[0])} words")
+        self._lengths(clouds=clouds, images=images, masks_out=masks_out)
+        width, ns = _cloud_table(clouds, none_allowed=False)
+        for s, n in enumerate(ns):
+            _mask_room(masks_out[s], s, n, "masks_out")
         rows, cols, stride = self._image_geometry(images)
-        if tuple(result_out.shape) != (S, 8) or result_out.element_size() != 4 or not result_out.is_contiguous():
-            raise ValueError(f"result_out must be a contiguous int32 tensor [{S}, 8]")
+        _result_tensor(result_out, (self.S, 8), 4, "result_out")
         lab = np.ascontiguousarray(labels, dtype=np.int32)
         vp = self._ptrs
         self._check(self._lib.mld_semantic_planes_estimate_device(
-            self._sp, vp(clouds), (C.c_int64 * S)(*[int(c.shape[0]) for c in clouds]), 4 * width, vp(images), rows, cols,
-            max(stride, cols), lab.ctypes.data, int(lab.size), float(inlier_threshold), int(result_out.data_ptr()), vp(masks_out)))
-        self._hold((list(clouds), list(images), result_out, list(masks_out)))
+            self._sp, vp(clouds), self._i64(ns), 4 * width, vp(images), rows, cols, max(stride, cols), lab.ctypes.data,
+            int(lab.size), float(inlier_threshold), int(result_out.data_ptr()), vp(masks_out)))
+        self._hold(clouds, images, result_out, masks_out)
 
 
 class RansacPlanes(_BatchObject):
@@ -517,45 +608,28 @@ class RansacPlanes(_BatchObject):
     asynchronous on the estimator's stream.  Close it before its estimator."""
 
     _NAME, _HANDLE = "ransac_planes", "_rp"
+    mask_words = staticmethod(mask_words)
 
     def __init__(self, estimator: DepthEstimator, n_seq: int, max_points: int, parameters=None):
         self.S, self.max_points = int(n_seq), int(max_points)
-        P = parameters if parameters is not None else estimator.getParameters()
-        self._create(estimator, self.S, self.max_points, C.byref(P))
-
-    @staticmethod
-    def mask_words(n_points: int) -> int:
-        """32-bit words of the inlier mask of a cloud of n_points."""
-        return (int(n_points) + 31) // 32
+        self._create(estimator, self.S, self.max_points, *self._calibration(estimator, "parameters", parameters=parameters))
 
     def estimate(self, clouds, seeds, result_out, masks_out):
         """clouds: S contiguous float32 CUDA tensors [n, 4] or [n, 8] of one width (an entry None: a sequence without
         points); seeds: S integers; result_out: an int32 CUDA tensor [S, 8] that receives the records
         (capi.MldRansacPlaneResult: coefficients as float bits, then n_inliers, iterations, status, n_candidates);
         masks_out: S int32 CUDA tensors of at least mask_words(n) entries (None where the cloud is)."""
-        S = self.S
-        for name, ts in (("clouds", clouds), ("seeds", seeds), ("masks_out", masks_out)):
-            if len(ts) != S:
-                raise ValueError(f"{name}: expected {S} entries, one per sequence")
-        width = next((int(cl.shape[1]) for cl in clouds if cl is not None), 4)
-        ns = []
-        for s, cl in enumerate(clouds):
-            if cl is None:
-                ns.append(0)
-                continue
-            if cl.dim() != 2 or int(cl.shape[1]) != width or width not in (4, 8) or not cl.is_contiguous() or cl.element_size() != 4:
-                raise ValueError("clouds: contiguous float32 [n, 4] or [n, 8], one width for all sequences")
-            ns.append(int(cl.shape[0]))
-            if ns[s] and (masks_out[s] is None or
-                          int(masks_out[s].numel()) * masks_out[s].element_size() < 4 * self.mask_words(ns[s])):
-                raise ValueError(f"sequence {s}: masks_out holds fewer than {self.mask_words(ns[s])} words")
-        if tuple(result_out.shape) != (S, 8) or result_out.element_size() != 4 or not result_out.is_contiguous():
-            raise ValueError(f"result_out must be a contiguous int32 tensor [{S}, 8]")
+        self._lengths(clouds=clouds, seeds=seeds, masks_out=masks_out)
+        width, ns = _cloud_table(clouds)
+        for s, n in enumerate(ns):
+            if n:
+                _mask_room(masks_out[s], s, n, "masks_out")
+        _result_tensor(result_out, (self.S, 8), 4, "result_out")
         vp = self._ptrs
         self._check(self._lib.mld_ransac_planes_estimate_device(
-            self._rp, vp(clouds), (C.c_int64 * S)(*ns), 4 * width, (C.c_uint32 * S)(*[int(x) & 0xFFFFFFFF for x in seeds]),
+            self._rp, vp(clouds), self._i64(ns), 4 * width, (C.c_uint32 * self.S)(*[int(x) & 0xFFFFFFFF for x in seeds]),
             int(result_out.data_ptr()), vp(masks_out)))
-        self._hold((list(clouds), result_out, list(masks_out)))
+        self._hold(clouds, result_out, masks_out)
 
 
 class ProjectedClouds(_BatchObject):
@@ -570,10 +644,7 @@ class ProjectedClouds(_BatchObject):
 
     def __init__(self, estimator: DepthEstimator, n_seq: int, max_points: int):
         self.S, self.max_points = int(n_seq), int(max_points)
-        cam = estimator._camera.as_struct()
-        self.width, self.height = int(cam.width), int(cam.height)
-        T = np.ascontiguousarray(np.asarray(estimator._T, dtype=np.float64).reshape(-1)[:12])
-        self._create(estimator, self.S, self.max_points, C.byref(cam), T.ctypes.data_as(C.POINTER(C.c_double)))
+        self._create(estimator, self.S, self.max_points, *self._calibration(estimator, "camera", "transform"))
 
     def export(self, clouds, capacity, n_visible, uv, index, depth=None, cam=None, pixel_map=None):
         """clouds: S contiguous float32 CUDA tensors [n, 4] or [n, 8] of one width (an entry None: a sequence without
@@ -584,49 +655,22 @@ class ProjectedClouds(_BatchObject):
         pixel_map: None, or S int32 CUDA tensors of height * width entries.  Single entries of uv and index may be None
         where min(capacity, n) is 0, of depth, cam and pixel_map anywhere.  Visible points at or beyond a sequence's
         capacity are dropped, which the caller sees from n_visible[s] > capacity[s]; the map is not affected."""
-        S = self.S
-        for name, ts in (("clouds", clouds), ("capacity", capacity), ("uv", uv), ("index", index), ("depth", depth),
-                         ("cam", cam), ("pixel_map", pixel_map)):
-            if ts is not None and len(ts) != S:
-                raise ValueError(f"{name}: expected {S} entries, one per sequence")
-        if tuple(n_visible.shape) != (S,) or n_visible.element_size() != 8 or not n_visible.is_contiguous():
-            raise ValueError(f"n_visible must be a contiguous int64 tensor [{S}]")
-        width = next((int(cl.shape[1]) for cl in clouds if cl is not None), 4)
-        ns, caps = [], []
-
-        def holds(ts, s, entries, size, name, required):
-            t = ts[s] if ts is not None else None
-            if t is None:
-                if required and entries:
-                    raise ValueError(f"sequence {s}: {name} is missing")
-                return
-            if t.element_size() != size or not t.is_contiguous() or int(t.numel()) < entries:
-                raise ValueError(f"sequence {s}: {name} must be contiguous, of {size}-byte elements, at least {entries} of them")
-
-        for s, cl in enumerate(clouds):
-            n = 0
-            if cl is not None:
-                if cl.dim() != 2 or int(cl.shape[1]) != width or width not in (4, 8) or not cl.is_contiguous() or cl.element_size() != 4:
-                    raise ValueError("clouds: contiguous float32 [n, 4] or [n, 8], one width for all sequences")
-                n = int(cl.shape[0])
-            cap = n if capacity is None else int(capacity[s])
-            if cap < 0:
-                raise ValueError(f"sequence {s}: negative capacity")
-            ns.append(n)
-            caps.append(cap)
-            m = min(cap, n)
-            holds(uv, s, 2 * m, 8, "uv", True)
-            holds(index, s, m, 4, "index", True)
-            holds(depth, s, m, 8, "depth", False)
-            holds(cam, s, 3 * n, 8, "cam", False)
-            holds(pixel_map, s, self.width * self.height, 4, "pixel_map", False)
-        vp = self._ptrs
+        self._lengths(clouds=clouds, capacity=capacity, uv=uv, index=index, depth=depth, cam=cam, pixel_map=pixel_map)
+        _result_tensor(n_visible, (self.S,), 8, "n_visible")
+        width, ns = _cloud_table(clouds)
+        caps = _capacities(capacity, ns)
+        for s, n in enumerate(ns):
+            m = min(caps[s], n)
+            _holds(_at(uv, s), s, 2 * m, 8, "uv", required=True)
+            _holds(_at(index, s), s, m, 4, "index", required=True)
+            _holds(_at(depth, s), s, m, 8, "depth")
+            _holds(_at(cam, s), s, 3 * n, 8, "cam")
+            _holds(_at(pixel_map, s), s, self.width * self.height, 4, "pixel_map")
+        vp, opt = self._ptrs, self._opt
         self._check(self._lib.mld_projected_clouds_export_device(
-            self._pc, vp(clouds), (C.c_int64 * S)(*ns), 4 * width, (C.c_int64 * S)(*caps), int(n_visible.data_ptr()), vp(uv),
-            vp(index), vp(depth) if depth is not None else None, vp(cam) if cam is not None else None,
-            vp(pixel_map) if pixel_map is not None else None))
-        self._hold((list(clouds), n_visible, list(uv), list(index), list(depth) if depth is not None else None,
-                    list(cam) if cam is not None else None, list(pixel_map) if pixel_map is not None else None))
+            self._pc, vp(clouds), self._i64(ns), 4 * width, self._i64(caps), int(n_visible.data_ptr()), vp(uv), vp(index),
+            opt(depth), opt(cam), opt(pixel_map)))
+        self._hold(clouds, n_visible, uv, index, depth, cam, pixel_map)
 
 
 class DepthReports(_BatchObject):
@@ -642,48 +686,38 @@ class DepthReports(_BatchObject):
 
     def __init__(self, estimator: DepthEstimator, n_seq: int, max_features: int):
         self.S, self.max_features = int(n_seq), int(max_features)
-        cam = estimator._camera.as_struct()
-        self._create(estimator, self.S, self.max_features, C.byref(cam))
+        self._create(estimator, self.S, self.max_features, *self._calibration(estimator, "camera"))
 
-    def _outputs(self, ns, types, report, capacity, points, feature):
-        """Checks what both calls share; returns the capacity table (None without points)."""
-        S = self.S
-        for name, ts in (("types", types), ("capacity", capacity), ("points", points), ("feature", feature)):
-            if ts is not None and len(ts) != S:
-                raise ValueError(f"{name}: expected {S} entries, one per sequence")
-        if tuple(report.shape) != (S, self.WORDS) or report.element_size() != 8 or not report.is_contiguous():
-            raise ValueError(f"report must be a contiguous int64 tensor [{S}, {self.WORDS}]")
-        caps = None
+    def _collect(self, fn, size, per, depth, types, report, capacity, points, feature, **coords):
+        """Both calls: `coords` are the feature tables in front of depth, of `per` x n entries of `size` bytes each."""
+        self._lengths(depth=depth, **coords)
+        ns = []
+        for s, d in enumerate(depth):
+            n = _entries(d)
+            _holds(d, s, n, size, "depth")
+            for name, ts in coords.items():
+                _holds(ts[s], s, per * n, size, name, required=True)
+                if ts[s] is not None and int(ts[s].numel()) != per * n:
+                    raise ValueError(f"sequence {s}: {name} must hold {per} x {n} entries, as depth does")
+            ns.append(n)
+        self._lengths(types=types, capacity=capacity, points=points, feature=feature)
+        _result_tensor(report, (self.S, self.WORDS), 8, "report")
         for s, n in enumerate(ns):
-            t = types[s] if types is not None else None
-            if t is not None and (t.element_size() != 4 or not t.is_contiguous() or int(t.numel()) != n):
-                raise ValueError(f"sequence {s}: types must be a contiguous int32 tensor of {n} entries")
-        if points is not None:
-            caps = []
+            _holds(_at(types, s), s, n, 4, "types")
+            if _at(types, s) is not None and int(types[s].numel()) != n:
+                raise ValueError(f"sequence {s}: types must hold {n} entries")
+        caps = None
+        if points is not None:  # (without points neither the capacities nor the feature table are looked at or passed)
+            caps = _capacities(capacity, ns)
             for s, n in enumerate(ns):
-                cap = n if capacity is None else int(capacity[s])
-                if cap < 0:
-                    raise ValueError(f"sequence {s}: negative capacity")
-                caps.append(cap)
-                m = min(cap, n)
-                for name, t, size, entries in (("points", points[s], 8, 3 * m),
-                                               ("feature", feature[s] if feature is not None else None, 4, m)):
-                    if t is None:
-                        if name == "points" and entries:
-                            raise ValueError(f"sequence {s}: points is missing")
-                        continue
-                    if t.element_size() != size or not t.is_contiguous() or int(t.numel()) < entries:
-                        raise ValueError(f"sequence {s}: {name} must be contiguous, of {size}-byte elements, at least {entries} of them")
-        return caps
-
-    def _inputs(self, s, n, size, **arrays):
-        for name, t in arrays.items():
-            if t is None:
-                if n:
-                    raise ValueError(f"sequence {s}: {name} is missing")
-                continue
-            if t.element_size() != size or not t.is_contiguous():
-                raise ValueError(f"sequence {s}: {name} must be contiguous, of {size}-byte elements")
+                m = min(caps[s], n)
+                _holds(points[s], s, 3 * m, 8, "points", required=True)
+                _holds(_at(feature, s), s, m, 4, "feature")
+        tables = tuple(coords.values()) + (depth,)
+        opt = self._opt
+        self._check(fn(self._dr, *[self._ptrs(ts) for ts in tables], opt(types), self._i64(ns), self._i64(caps),
+                       int(report.data_ptr()), opt(points), opt(feature) if points is not None else None))
+        self._hold(*tables, types, report, points, feature)
 
     def collect(self, uv, depth, types, report, capacity=None, points=None, feature=None):
         """uv: S contiguous float64 CUDA tensors [n, 2] (an entry None: a sequence without features); depth: S float64
@@ -693,49 +727,13 @@ class DepthReports(_BatchObject):
         [capacity, 3]); capacity: S integers, or None (= n, never truncated); feature: None, or S int32 CUDA tensors of
         at least min(capacity, n) entries (single entries may be None).  Points at or beyond a sequence's capacity are
         dropped, which the caller sees from n_interpolated > capacity."""
-        S = self.S
-        for name, ts in (("uv", uv), ("depth", depth)):
-            if len(ts) != S:
-                raise ValueError(f"{name}: expected {S} entries, one per sequence")
-        ns = []
-        for s in range(S):
-            n = int(depth[s].numel()) if depth[s] is not None else 0
-            self._inputs(s, n, 8, uv=uv[s], depth=depth[s])
-            if uv[s] is not None and int(uv[s].numel()) != 2 * n:
-                raise ValueError(f"sequence {s}: uv must hold 2 x {n} entries")
-            ns.append(n)
-        caps = self._outputs(ns, types, report, capacity, points, feature)
-        vp = self._ptrs
-        self._check(self._lib.mld_depth_reports_collect_device(
-            self._dr, vp(uv), vp(depth), vp(types) if types is not None else None, (C.c_int64 * S)(*ns),
-            (C.c_int64 * S)(*caps) if caps is not None else None, int(report.data_ptr()),
-            vp(points) if points is not None else None, vp(feature) if feature is not None and points is not None else None))
-        self._hold((list(uv), list(depth), list(types) if types is not None else None, report,
-                    list(points) if points is not None else None, list(feature) if feature is not None else None))
+        self._collect(self._lib.mld_depth_reports_collect_device, 8, 2, depth, types, report, capacity, points, feature, uv=uv)
 
     def collect_tracks(self, u, v, depth, types, report, capacity=None, points=None, feature=None):
         """As collect(), on the tensors of TrackletBatch.prepare_step() / prepare(): u, v (u_new, v_new), depth (d_cur):
         S float32 CUDA tensors [n]; types (t_cur): None, or S int32 CUDA tensors [n]."""
-        S = self.S
-        for name, ts in (("u", u), ("v", v), ("depth", depth)):
-            if len(ts) != S:
-                raise ValueError(f"{name}: expected {S} entries, one per sequence")
-        ns = []
-        for s in range(S):
-            n = int(depth[s].numel()) if depth[s] is not None else 0
-            self._inputs(s, n, 4, u=u[s], v=v[s], depth=depth[s])
-            for name, t in (("u", u[s]), ("v", v[s])):
-                if t is not None and int(t.numel()) != n:
-                    raise ValueError(f"sequence {s}: {name} and depth differ in length")
-            ns.append(n)
-        caps = self._outputs(ns, types, report, capacity, points, feature)
-        vp = self._ptrs
-        self._check(self._lib.mld_depth_reports_collect_tracks_device(
-            self._dr, vp(u), vp(v), vp(depth), vp(types) if types is not None else None, (C.c_int64 * S)(*ns),
-            (C.c_int64 * S)(*caps) if caps is not None else None, int(report.data_ptr()),
-            vp(points) if points is not None else None, vp(feature) if feature is not None and points is not None else None))
-        self._hold((list(u), list(v), list(depth), list(types) if types is not None else None, report,
-                    list(points) if points is not None else None, list(feature) if feature is not None else None))
+        self._collect(self._lib.mld_depth_reports_collect_tracks_device, 4, 1, depth, types, report, capacity, points, feature,
+                      u=u, v=v)
 
 
 class PlaneInliers(_BatchObject):
@@ -749,17 +747,12 @@ class PlaneInliers(_BatchObject):
     stream.  Close it before its estimator."""
 
     _NAME, _HANDLE = "plane_inliers", "_pi"
+    mask_words = staticmethod(mask_words)
 
     def __init__(self, estimator: DepthEstimator, n_seq: int, max_points: int, parameters=None):
         self.S, self.max_points = int(n_seq), int(max_points)
-        P = parameters if parameters is not None else estimator.getParameters()
-        T = np.ascontiguousarray(np.asarray(estimator._T, dtype=np.float64).reshape(-1)[:12])
-        self._create(estimator, self.S, self.max_points, C.byref(P), T.ctypes.data_as(C.POINTER(C.c_double)))
-
-    @staticmethod
-    def mask_words(n_points: int) -> int:
-        """32-bit words of the inlier mask of a cloud of n_points."""
-        return (int(n_points) + 31) // 32
+        self._create(estimator, self.S, self.max_points,
+                     *self._calibration(estimator, "parameters", "transform", parameters=parameters))
 
     def export(self, clouds, masks, capacity, counts, index, lidar=None, cam=None):
         """clouds: S contiguous float32 CUDA tensors [n, 4] or [n, 8] of one width (an entry None: a sequence without
@@ -769,47 +762,21 @@ class PlaneInliers(_BatchObject):
         min(capacity, n) entries (a contiguous [capacity, 3]); cam: None, or S float64 CUDA tensors of that length.
         Single entries of index may be None where min(capacity, n) is 0, of lidar and cam anywhere.  Inliers (cloud
         points) at or beyond a sequence's capacity are dropped, which the caller sees from the counts."""
-        S = self.S
-        for name, ts in (("clouds", clouds), ("masks", masks), ("capacity", capacity), ("index", index), ("lidar", lidar),
-                         ("cam", cam)):
-            if ts is not None and len(ts) != S:
-                raise ValueError(f"{name}: expected {S} entries, one per sequence")
-        if tuple(counts.shape) != (S, 2) or counts.element_size() != 8 or not counts.is_contiguous():
-            raise ValueError(f"counts must be a contiguous int64 tensor [{S}, 2]")
-        width = next((int(cl.shape[1]) for cl in clouds if cl is not None), 4)
-        ns, caps = [], []
-
-        def holds(ts, s, entries, size, name, required):
-            t = ts[s] if ts is not None else None
-            if t is None:
-                if required and entries:
-                    raise ValueError(f"sequence {s}: {name} is missing")
-                return
-            if t.element_size() != size or not t.is_contiguous() or int(t.numel()) < entries:
-                raise ValueError(f"sequence {s}: {name} must be contiguous, of {size}-byte elements, at least {entries} of them")
-
-        for s, cl in enumerate(clouds):
-            n = 0
-            if cl is not None:
-                if cl.dim() != 2 or int(cl.shape[1]) != width or width not in (4, 8) or not cl.is_contiguous() or cl.element_size() != 4:
-                    raise ValueError("clouds: contiguous float32 [n, 4] or [n, 8], one width for all sequences")
-                n = int(cl.shape[0])
-            cap = n if capacity is None else int(capacity[s])
-            if cap < 0:
-                raise ValueError(f"sequence {s}: negative capacity")
-            ns.append(n)
-            caps.append(cap)
-            m = min(cap, n)
-            holds(masks, s, self.mask_words(n), 4, "masks", True)
-            holds(index, s, m, 4, "index", True)
-            holds(lidar, s, 3 * m, 4, "lidar", False)
-            holds(cam, s, 3 * m, 8, "cam", False)
-        vp = self._ptrs
+        self._lengths(clouds=clouds, masks=masks, capacity=capacity, index=index, lidar=lidar, cam=cam)
+        _result_tensor(counts, (self.S, 2), 8, "counts")
+        width, ns = _cloud_table(clouds)
+        caps = _capacities(capacity, ns)
+        for s, n in enumerate(ns):
+            m = min(caps[s], n)
+            _holds(_at(masks, s), s, mask_words(n), 4, "masks", required=True)
+            _holds(_at(index, s), s, m, 4, "index", required=True)
+            _holds(_at(lidar, s), s, 3 * m, 4, "lidar")
+            _holds(_at(cam, s), s, 3 * m, 8, "cam")
+        vp, opt = self._ptrs, self._opt
         self._check(self._lib.mld_plane_inliers_export_device(
-            self._pi, vp(clouds), (C.c_int64 * S)(*ns), 4 * width, vp(masks), (C.c_int64 * S)(*caps), int(counts.data_ptr()),
-            vp(index), vp(lidar) if lidar is not None else None, vp(cam) if cam is not None else None))
-        self._hold((list(clouds), list(masks), counts, list(index), list(lidar) if lidar is not None else None,
-                    list(cam) if cam is not None else None))
+            self._pi, vp(clouds), self._i64(ns), 4 * width, vp(masks), self._i64(caps), int(counts.data_ptr()), vp(index),
+            opt(lidar), opt(cam)))
+        self._hold(clouds, masks, counts, index, lidar, cam)
 
 
 class FeatureTraces(_BatchObject):
@@ -829,11 +796,8 @@ class FeatureTraces(_BatchObject):
 
     def __init__(self, estimator: DepthEstimator, n_seq: int, max_features: int, parameters=None):
         self.S, self.max_features = int(n_seq), int(max_features)
-        P = parameters if parameters is not None else estimator.getParameters()
-        cam = estimator._camera.as_struct()
-        self.width, self.height = int(cam.width), int(cam.height)
-        T = np.ascontiguousarray(np.asarray(estimator._T, dtype=np.float64).reshape(-1)[:12])
-        self._create(estimator, self.S, self.max_features, C.byref(P), C.byref(cam), T.ctypes.data_as(C.POINTER(C.c_double)))
+        self._create(estimator, self.S, self.max_features,
+                     *self._calibration(estimator, "parameters", "camera", "transform", parameters=parameters))
 
     @classmethod
     def records(cls, trace) -> np.ndarray:
@@ -842,52 +806,27 @@ class FeatureTraces(_BatchObject):
         return np.ascontiguousarray(trace.cpu().numpy()).reshape(-1).view(cls.DTYPE)
 
     def _collect(self, ns, feats, maps, index, cam, trace, coeffs, masks, list_capacity, lists):
-        S, cap = self.S, int(list_capacity)
+        cap = int(list_capacity)
         names = ("nb", "seg", "road", "road_inl")
-        for name, ts in (("pixel_map", maps), ("index", index), ("cam", cam), ("trace", trace), ("masks", masks)) + tuple(zip(names, lists)):
-            if ts is not None and len(ts) != S:
-                raise ValueError(f"{name}: expected {S} entries, one per sequence")
+        self._lengths(pixel_map=maps, index=index, cam=cam, trace=trace, masks=masks, **dict(zip(names, lists)))
         if not 0 <= cap <= self.MAX_LIST:
             raise ValueError(f"list_capacity must be in 0 .. {self.MAX_LIST}")
-        if (coeffs is None) != (masks is None):
-            raise ValueError("coeffs and masks come together or not at all")
-
-        def holds(t, s, entries, size, name):
-            if t is None:
-                raise ValueError(f"sequence {s}: {name} is missing")
-            if t.element_size() != size or not t.is_contiguous() or int(t.numel()) < entries:
-                raise ValueError(f"sequence {s}: {name} must be contiguous, of {size}-byte elements, at least {entries} of them")
-
-        n_idx, n_pts = [], []
+        planes = self._plane_args(coeffs, masks)
         for s, n in enumerate(ns):
-            n_idx.append(int(index[s].numel()) if index[s] is not None else 0)
-            n_pts.append(int(cam[s].numel()) // 3 if cam[s] is not None else 0)
-            if n == 0:
+            if n == 0:  # (nothing of a sequence without features is looked at)
                 continue
-            holds(maps[s], s, self.width * self.height, 4, "pixel_map")
-            if index[s] is not None:
-                holds(index[s], s, 0, 4, "index")
-            if cam[s] is not None:
-                holds(cam[s], s, 0, 8, "cam")
-            holds(trace[s], s, self.WORDS * n, 8, "trace")
+            _holds(maps[s], s, self.width * self.height, 4, "pixel_map", required=True)
+            _holds(index[s], s, 0, 4, "index")
+            _holds(cam[s], s, 0, 8, "cam")
+            _holds(trace[s], s, self.WORDS * n, 8, "trace", required=True)
             for name, ts in zip(names, lists):
-                if cap and ts is not None and ts[s] is not None:
-                    holds(ts[s], s, cap * n, 4, name)
-        co = None
-        if coeffs is not None:
-            co = np.ascontiguousarray(coeffs, dtype=np.float32).reshape(S, 4)
+                if cap:
+                    _holds(_at(ts, s), s, cap * n, 4, name)
         vp = self._ptrs
-        tail = (vp(maps), vp(index), (C.c_int64 * S)(*n_idx), vp(cam), (C.c_int64 * S)(*n_pts),
-                co.ctypes.data_as(C.POINTER(C.c_float)) if co is not None else None, vp(masks) if masks is not None else None,
-                cap, vp(trace)) + tuple(vp(ts) if ts is not None else None for ts in lists)
-        nf = (C.c_int64 * S)(*ns)
-        if len(feats) == 1:
-            rc = self._lib.mld_feature_traces_collect_device(self._ft, vp(feats[0]), nf, *tail)
-        else:
-            rc = self._lib.mld_feature_traces_collect_tracks_device(self._ft, vp(feats[0]), vp(feats[1]), nf, *tail)
-        self._check(rc)
-        self._hold(([list(t) for t in feats], list(maps), list(index), list(cam), list(trace),
-                    list(masks) if masks is not None else None, [list(ts) if ts is not None else None for ts in lists]))
+        fn = self._lib.mld_feature_traces_collect_device if len(feats) == 1 else self._lib.mld_feature_traces_collect_tracks_device
+        self._check(fn(self._ft, *[vp(t) for t in feats], self._i64(ns), vp(maps), vp(index), self._i64(_entries(t) for t in index),
+                       vp(cam), self._i64(_entries(t, 3) for t in cam), *planes, cap, vp(trace), *[self._opt(ts) for ts in lists]))
+        self._hold(*feats, maps, index, cam, trace, masks, *lists)
 
     def collect(self, uv, pixel_map, index, cam, trace, coeffs=None, masks=None, list_capacity: int = 0, nb=None, seg=None,
                 road=None, road_inl=None):
@@ -898,30 +837,28 @@ class FeatureTraces(_BatchObject):
         tensors, an entry None: that sequence has no plane): both or neither; nb, seg, road, road_inl: None, or S int32
         CUDA tensors of at least list_capacity * n entries (a contiguous [n, list_capacity]; single entries may be None).
         A row receives the first min(count, list_capacity) entries of its list; the counts of the record are complete."""
-        if len(uv) != self.S:
-            raise ValueError(f"uv: expected {self.S} entries, one per sequence")
-        ns = []
+        self._lengths(uv=uv)
         for s, t in enumerate(uv):
-            if t is not None and (t.element_size() != 8 or not t.is_contiguous() or int(t.numel()) % 2):
+            _holds(t, s, 0, 8, "uv")
+            if _entries(t) % 2:
                 raise ValueError(f"sequence {s}: uv must be a contiguous float64 tensor [n, 2]")
-            ns.append(int(t.numel()) // 2 if t is not None else 0)
-        self._collect(ns, (uv,), pixel_map, index, cam, trace, coeffs, masks, list_capacity, (nb, seg, road, road_inl))
+        self._collect([_entries(t, 2) for t in uv], (uv,), pixel_map, index, cam, trace, coeffs, masks, list_capacity,
+                      (nb, seg, road, road_inl))
 
     def collect_tracks(self, u, v, pixel_map, index, cam, trace, coeffs=None, masks=None, list_capacity: int = 0, nb=None,
                        seg=None, road=None, road_inl=None):
         """As collect(), on the tensors of TrackletBatch.prepare_step() / prepare(): u, v (u_new, v_new): S float32 CUDA
         tensors [n]."""
-        if len(u) != self.S or len(v) != self.S:
-            raise ValueError(f"u, v: expected {self.S} entries, one per sequence")
-        ns = []
+        self._lengths(u=u, v=v)
         for s, (a, b) in enumerate(zip(u, v)):
             if (a is None) != (b is None):
                 raise ValueError(f"sequence {s}: u and v come together")
-            for t in (a, b):
-                if t is not None and (t.element_size() != 4 or not t.is_contiguous() or int(t.numel()) != int(a.numel())):
-                    raise ValueError(f"sequence {s}: u and v must be contiguous float32 tensors of one length")
-            ns.append(int(a.numel()) if a is not None else 0)
-        self._collect(ns, (u, v), pixel_map, index, cam, trace, coeffs, masks, list_capacity, (nb, seg, road, road_inl))
+            _holds(a, s, 0, 4, "u")
+            _holds(b, s, 0, 4, "v")
+            if _entries(b) != _entries(a):
+                raise ValueError(f"sequence {s}: u and v must be contiguous float32 tensors of one length")
+        self._collect([_entries(a) for a in u], (u, v), pixel_map, index, cam, trace, coeffs, masks, list_capacity,
+                      (nb, seg, road, road_inl))
 
 
 class CoverageMaps(_BatchObject):
@@ -940,11 +877,7 @@ class CoverageMaps(_BatchObject):
 
     def __init__(self, estimator: DepthEstimator, n_seq: int, parameters=None):
         self.S = int(n_seq)
-        P = parameters if parameters is not None else estimator.getParameters()
-        cam = estimator._camera.as_struct()
-        self.width, self.height = int(cam.width), int(cam.height)
-        T = np.ascontiguousarray(np.asarray(estimator._T, dtype=np.float64).reshape(-1)[:12])
-        self._create(estimator, self.S, C.byref(P), C.byref(cam), T.ctypes.data_as(C.POINTER(C.c_double)))
+        self._create(estimator, self.S, *self._calibration(estimator, "parameters", "camera", "transform", parameters=parameters))
 
     @classmethod
     def records(cls, record) -> np.ndarray:
@@ -967,52 +900,28 @@ class CoverageMaps(_BatchObject):
         None or (bucket_w, bucket_h) with bucket_out: S int32 CUDA tensors (a contiguous [capacity, 3] each, rows (x, y,
         n_nb); an entry None: capacity 0).  A sequence's first min(buckets, capacity) rows are written; n_buckets of the
         record is complete."""
-        S, cells = self.S, self.width * self.height
+        cells = self.width * self.height
         maps = (nb, road, road_inl, road_far, reach)
-        for name, ts in (("pixel_map", pixel_map), ("index", index), ("cam", cam), ("masks", masks), ("bucket_out", bucket_out)) + \
-                tuple(zip(self.MAPS, maps)):
-            if ts is not None and len(ts) != S:
-                raise ValueError(f"{name}: expected {S} entries, one per sequence")
-        if (coeffs is None) != (masks is None):
-            raise ValueError("coeffs and masks come together or not at all")
+        self._lengths(pixel_map=pixel_map, index=index, cam=cam, masks=masks, bucket_out=bucket_out, **dict(zip(self.MAPS, maps)))
+        planes = self._plane_args(coeffs, masks)
         if (bucket is None) != (bucket_out is None):
             raise ValueError("bucket and bucket_out come together or not at all")
-
-        def holds(t, s, entries, size, name):
-            if t is None:
-                raise ValueError(f"sequence {s}: {name} is missing")
-            if t.element_size() != size or not t.is_contiguous() or int(t.numel()) < entries:
-                raise ValueError(f"sequence {s}: {name} must be contiguous, of {size}-byte elements, at least {entries} of them")
-
-        holds(record, "*", self.WORDS * S, 8, "record")
-        n_idx, n_pts, caps = [], [], []
-        for s in range(S):
-            holds(pixel_map[s], s, cells, 4, "pixel_map")
-            if index[s] is not None:
-                holds(index[s], s, 0, 4, "index")
-            if cam[s] is not None:
-                holds(cam[s], s, 0, 8, "cam")
-            n_idx.append(int(index[s].numel()) if index[s] is not None else 0)
-            n_pts.append(int(cam[s].numel()) // 3 if cam[s] is not None else 0)
+        _holds(record, "*", self.WORDS * self.S, 8, "record", required=True)
+        for s in range(self.S):
+            _holds(pixel_map[s], s, cells, 4, "pixel_map", required=True)
+            _holds(index[s], s, 0, 4, "index")
+            _holds(cam[s], s, 0, 8, "cam")
             for name, ts in zip(self.MAPS, maps):
-                if ts is not None and ts[s] is not None:
-                    holds(ts[s], s, cells, 1, name)
-            if bucket_out is not None:
-                if bucket_out[s] is not None:
-                    holds(bucket_out[s], s, 0, 4, "bucket_out")
-                caps.append(int(bucket_out[s].numel()) // 3 if bucket_out[s] is not None else 0)
-        co = None
-        if coeffs is not None:
-            co = np.ascontiguousarray(coeffs, dtype=np.float32).reshape(S, 4)
+                _holds(_at(ts, s), s, cells, 1, name)
+            _holds(_at(bucket_out, s), s, 0, 4, "bucket_out")
         bw, bh = (int(bucket[0]), int(bucket[1])) if bucket is not None else (0, 0)
-        vp = self._ptrs
+        caps = [_entries(t, 3) for t in bucket_out] if bucket_out is not None else None
+        vp, opt = self._ptrs, self._opt
         self._check(self._lib.mld_coverage_maps_collect_device(
-            self._cm, vp(pixel_map), vp(index), (C.c_int64 * S)(*n_idx), vp(cam), (C.c_int64 * S)(*n_pts),
-            co.ctypes.data_as(C.POINTER(C.c_float)) if co is not None else None, vp(masks) if masks is not None else None,
-            *[vp(ts) if ts is not None else None for ts in maps], int(record.data_ptr()), bw, bh,
-            (C.c_int64 * S)(*caps) if bucket_out is not None else None, vp(bucket_out) if bucket_out is not None else None))
-        self._hold((list(pixel_map), list(index), list(cam), record, list(masks) if masks is not None else None,
-                    [list(ts) if ts is not None else None for ts in maps], list(bucket_out) if bucket_out is not None else None))
+            self._cm, vp(pixel_map), vp(index), self._i64(_entries(t) for t in index), vp(cam),
+            self._i64(_entries(t, 3) for t in cam), *planes, *[opt(ts) for ts in maps], int(record.data_ptr()), bw, bh,
+            self._i64(caps), opt(bucket_out)))
+        self._hold(pixel_map, index, cam, record, masks, *maps, bucket_out)
 
 
 class TrackletBatch:
@@ -1025,7 +934,21 @@ class TrackletBatch:
     The sequences are LANES that start, restart and resume independently: `lane_has_last[s]` says whether the previous
     bank holds a previous frame of lane s (every lane has one after a step; set_previous() gives one to a resumed lane),
     and step(restart=...) / run(restart=...) start a new recording in a lane - the construction of a new
-    TrackletDepthModule.  `have_last` is true when every lane has a previous frame; assigning it sets every lane."""
+    TrackletDepthModule.  `have_last` is true when every lane has a previous frame; assigning it sets every lane.
+
+    The objects of _ATTACHABLE hang on the batch under their attribute (None until attach_*() made them)."""
+
+    # attribute: (class, its attach method, attributes of the batch that follow (estimator, S) in the constructor).  The
+    # attach_* methods, the guard of the methods that need an object and close(), in this order, go by this table.
+    _ATTACHABLE = {"semantic_labels": (SemanticLabels, "attach_labels", ()),
+                   "store": (TrackletStore, "attach_store", ("max_tracks",)),
+                   "planes": (SemanticPlanes, "attach_planes", ()),
+                   "rplanes": (RansacPlanes, "attach_ransac_planes", ()),
+                   "pclouds": (ProjectedClouds, "attach_projected_clouds", ()),
+                   "depth_reports": (DepthReports, "attach_reports", ("max_tracks",)),
+                   "inliers": (PlaneInliers, "attach_plane_inliers", ()),
+                   "feature_traces": (FeatureTraces, "attach_traces", ("max_tracks",)),
+                   "coverage_maps": (CoverageMaps, "attach_coverage", ())}
 
     def __init__(self, parameters, camera: CameraPinhole, transform_lidar_to_cam, n_seq: int, max_tracks: int,
                  device: int = 0, list_capacity=None):
@@ -1041,15 +964,23 @@ class TrackletBatch:
         self._keep_previous = ([], [])  # tensors of set_previous(): held like `_keep`, until their slot is overwritten
         self._slot_set = [[False] * self.S, [False] * self.S]  # per bank and lane: has the slot ever held a cloud?
         self.max_tracks = int(max_tracks)
-        self.store: Optional[TrackletStore] = None
-        self.semantic_labels: Optional[SemanticLabels] = None
-        self.planes: Optional[SemanticPlanes] = None
-        self.rplanes: Optional[RansacPlanes] = None
-        self.pclouds: Optional[ProjectedClouds] = None
-        self.depth_reports: Optional[DepthReports] = None
-        self.inliers: Optional[PlaneInliers] = None
-        self.feature_traces: Optional[FeatureTraces] = None
-        self.coverage_maps: Optional[CoverageMaps] = None
+        for attr in self._ATTACHABLE:
+            setattr(self, attr, None)
+
+    def _attach(self, attr, *args):
+        """The object of `attr`, made on the first call from (estimator, S, the table's attributes, *args)."""
+        if getattr(self, attr) is None:
+            cls, _, own = self._ATTACHABLE[attr]
+            setattr(self, attr, cls(self.est, self.S, *[getattr(self, a) for a in own], *args))
+        return getattr(self, attr)
+
+    def _attached(self, attr, method):
+        """The object of `attr` for `method`, which cannot run without it."""
+        obj = getattr(self, attr)
+        if obj is None:
+            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED,
+                                      f"TrackletBatch.{method} without {self._ATTACHABLE[attr][1]}")
+        return obj
 
     @property
     def have_last(self) -> bool:
@@ -1086,6 +1017,15 @@ class TrackletBatch:
                     f["coeffs"][q].ctypes.data_as(C.POINTER(C.c_float)), (C.c_void_p * 1)(f["masks"][q])))
                 self._slot_set[1 - self.bank][q] = True
 
+    def _release(self, nxt, handover):
+        """Lets the batch `nxt` (None or this one: nobody) start behind what this one has queued so far - at the end of
+        this projection, or behind this step's classification kernel (include/mld.h "Two contexts")."""
+        if nxt is not None and nxt is not self:
+            if handover == "classify":
+                nxt.est.orderAfterClassify(self.est)
+            else:
+                nxt.est.orderAfter(self.est)
+
     def _stepped(self, f):
         """The arrays must outlive the asynchronous launches; the previous frame's clouds stay referenced by their slots."""
         self._keep = (self._keep[1] if self._keep else None, f)
@@ -1114,9 +1054,21 @@ class TrackletBatch:
     def attach_planes(self, max_points: int = 1 << 19) -> SemanticPlanes:
         """The semantic ground plane estimator of the S sequences that semantic_planes() runs ahead of a step, for clouds
         of up to max_points points (default: 128 beams x 4096, 320 KB of scratch per sequence)."""
-        if self.planes is None:
-            self.planes = SemanticPlanes(self.est, self.S, max_points)
-        return self.planes
+        return self._attach("planes", max_points)
+
+    def _estimated_planes(self, clouds, estimate):
+        """estimate(result_out, masks_out) on fresh tensors for `clouds`, then ONE device-to-host copy of 32 * S bytes and
+        one synchronisation: (coeffs float32 [S, 4], masks, the int32 [S, 8] records on the host)."""
+        import torch
+        dev = clouds[0].device
+        masks = [torch.empty(max(1, mask_words(c.shape[0])), dtype=torch.int32, device=dev) for c in clouds]
+        res = torch.empty((self.S, 8), dtype=torch.int32, device=dev)
+        self.est._after_torch(clouds[0])
+        estimate(res, masks)
+        host = np.empty((self.S, 8), dtype=np.int32)
+        self.est._check(self.est._lib.mld_synchronize(self.est._ctx))
+        host[:] = res.cpu().numpy()
+        return np.ascontiguousarray(host[:, :4]).view(np.float32), masks, host
 
     def semantic_planes(self, clouds, images, labels=(6, 7, 8, 9), threshold: Optional[float] = None):
         """The ground planes process() builds from the label images (tracklet_depth_module.cpp:269-284: labels 6..9,
@@ -1126,29 +1078,18 @@ class TrackletBatch:
         synchronisation per batch: mld_set_clouds_planes_range_device takes the coefficients from the host.  A
         sequence with status 1 (the reference's ExceptionPclInvalid) has zero coefficients and an empty mask; what to do
         with its frame is the caller's decision.  attach_planes() first."""
-        import torch
-        if self.planes is None:
-            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.semantic_planes without attach_planes")
+        planes = self._attached("planes", "semantic_planes")
         if threshold is None:
             threshold = self.est.getParameters().ransac_plane_refinement_treshold
-        dev = clouds[0].device
-        masks = [torch.empty(max(1, SemanticPlanes.mask_words(c.shape[0])), dtype=torch.int32, device=dev) for c in clouds]
-        res = torch.empty((self.S, 8), dtype=torch.int32, device=dev)
-        self.est._after_torch(clouds[0])
-        self.planes.estimate(clouds, images, labels, threshold, res, masks)
-        host = np.empty((self.S, 8), dtype=np.int32)
-        self.est._check(self.est._lib.mld_synchronize(self.est._ctx))
-        host[:] = res.cpu().numpy()
-        coeffs = np.ascontiguousarray(host[:, :4]).view(np.float32)
+        coeffs, masks, host = self._estimated_planes(
+            clouds, lambda res, masks: planes.estimate(clouds, images, labels, threshold, res, masks))
         return coeffs, masks, host[:, 6].copy(), host[:, 4:6].copy()
 
     def attach_ransac_planes(self, max_points: int = 1 << 19) -> RansacPlanes:
         """The RANSAC ground plane estimator of the S sequences that ransac_planes() runs ahead of a step - for frames
         without a label image -, for clouds of up to max_points points (default: 128 beams x 4096, 66 KB of scratch per
         sequence).  It takes the estimator's parameters as they are now."""
-        if self.rplanes is None:
-            self.rplanes = RansacPlanes(self.est, self.S, max_points)
-        return self.rplanes
+        return self._attach("rplanes", max_points)
 
     def ransac_planes(self, clouds, seeds):
         """The ground planes setInputCloud estimates by default (RansacPlane::CalculateInliersPlane, parameters
@@ -1157,26 +1098,14 @@ class TrackletBatch:
         One call on the GPU, then ONE device-to-host copy of 32 * S bytes and one synchronisation per batch, as
         semantic_planes().  A sequence with status 1 (the reference's ExceptionPclInvalid) has zero coefficients and an
         empty mask; what to do with its frame is the caller's decision.  attach_ransac_planes() first."""
-        import torch
-        if self.rplanes is None:
-            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.ransac_planes without attach_ransac_planes")
-        dev = clouds[0].device
-        masks = [torch.empty(max(1, RansacPlanes.mask_words(c.shape[0])), dtype=torch.int32, device=dev) for c in clouds]
-        res = torch.empty((self.S, 8), dtype=torch.int32, device=dev)
-        self.est._after_torch(clouds[0])
-        self.rplanes.estimate(clouds, seeds, res, masks)
-        host = np.empty((self.S, 8), dtype=np.int32)
-        self.est._check(self.est._lib.mld_synchronize(self.est._ctx))
-        host[:] = res.cpu().numpy()
-        coeffs = np.ascontiguousarray(host[:, :4]).view(np.float32)
+        rplanes = self._attached("rplanes", "ransac_planes")
+        coeffs, masks, host = self._estimated_planes(clouds, lambda res, masks: rplanes.estimate(clouds, seeds, res, masks))
         return coeffs, masks, host[:, 6].copy(), np.ascontiguousarray(host[:, [7, 4, 5]])
 
     def attach_projected_clouds(self, max_points: int = 1 << 19) -> ProjectedClouds:
         """The export of the projected clouds of the S sequences that projected_clouds() runs, for clouds of up to
         max_points points (default: 128 beams x 4096, 66 KB of scratch per sequence)."""
-        if self.pclouds is None:
-            self.pclouds = ProjectedClouds(self.est, self.S, max_points)
-        return self.pclouds
+        return self._attach("pclouds", max_points)
 
     def projected_clouds(self, clouds, depth: bool = False, cam: bool = False, pixel_map: bool = False, capacity=None):
         """The PointcloudData of this frame's clouds as device tensors - what the ROS layer's PublishImageProjectionCloud
@@ -1187,13 +1116,10 @@ class TrackletBatch:
         wait for the export, so torch operations may consume the tensors at once; a host read synchronises as usual.
         attach_projected_clouds() first."""
         import torch
-        if self.pclouds is None:
-            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED,
-                                      "TrackletBatch.projected_clouds without attach_projected_clouds")
-        pc = self.pclouds
+        pc = self._attached("pclouds", "projected_clouds")
         dev = next((c.device for c in clouds if c is not None), torch.device("cuda", self.est._device))
         ns = [int(c.shape[0]) if c is not None else 0 for c in clouds]
-        caps = [min(int(capacity[s]), ns[s]) if capacity is not None else ns[s] for s in range(self.S)]
+        caps = _capacities(capacity, ns, clamp=True)
         out = {"n_visible": torch.empty(self.S, dtype=torch.int64, device=dev),
                "uv": [torch.empty((m, 2), dtype=torch.float64, device=dev) for m in caps],
                "index": [torch.empty(m, dtype=torch.int32, device=dev) for m in caps],
@@ -1209,9 +1135,7 @@ class TrackletBatch:
         """The export of the ground-plane inliers of the S sequences that plane_inliers() runs, for clouds of up to
         max_points points (default: 128 beams x 4096, 4 KB of scratch per sequence, 68 KB with the camx filter on).  It
         takes the estimator's parameters as they are now."""
-        if self.inliers is None:
-            self.inliers = PlaneInliers(self.est, self.S, max_points)
-        return self.inliers
+        return self._attach("inliers", max_points)
 
     def plane_inliers(self, clouds, masks, lidar: bool = False, cam: bool = False, capacity=None):
         """The inliers of this frame's ground planes as device tensors, from the masks exactly as semantic_planes() /
@@ -1223,26 +1147,23 @@ class TrackletBatch:
         current stream is made to wait for the export, so torch operations may consume the tensors at once; a host read
         synchronises as usual.  attach_plane_inliers() first."""
         import torch
-        if self.inliers is None:
-            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.plane_inliers without attach_plane_inliers")
+        inliers = self._attached("inliers", "plane_inliers")
         dev = next((c.device for c in clouds if c is not None), torch.device("cuda", self.est._device))
         ns = [int(c.shape[0]) if c is not None else 0 for c in clouds]
-        caps = [min(int(capacity[s]), ns[s]) if capacity is not None else ns[s] for s in range(self.S)]
+        caps = _capacities(capacity, ns, clamp=True)
         out = {"counts": torch.empty((self.S, 2), dtype=torch.int64, device=dev),
                "index": [torch.empty(m, dtype=torch.int32, device=dev) for m in caps],
                "lidar": [torch.empty((m, 3), dtype=torch.float32, device=dev) for m in caps] if lidar else None,
                "cam": [torch.empty((m, 3), dtype=torch.float64, device=dev) for m in caps] if cam else None}
         self.est._after_torch(*[c for c in clouds if c is not None][:1])
-        self.inliers.export(clouds, masks, caps, out["counts"], out["index"], out["lidar"], out["cam"])
+        inliers.export(clouds, masks, caps, out["counts"], out["index"], out["lidar"], out["cam"])
         self.est.orderTorchAfter()
         return out
 
     def attach_reports(self) -> DepthReports:
         """The statistics and interpolated clouds of the S sequences that reports() queues behind a step, for up to
         max_tracks tracks per sequence."""
-        if self.depth_reports is None:
-            self.depth_reports = DepthReports(self.est, self.S, self.max_tracks)
-        return self.depth_reports
+        return self._attach("depth_reports")
 
     def reports(self, f, points: bool = False, capacity=None):
         """The depth-calculation statistics of the tracks of table `f` (prepare_step() / prepare()) and, with points, their
@@ -1255,28 +1176,23 @@ class TrackletBatch:
         torch's current stream is made to wait for the call, so torch operations may consume the tensors at once; a
         host read synchronises as usual.  attach_reports() first."""
         import torch
-        if self.depth_reports is None:
-            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.reports without attach_reports")
+        reports = self._attached("depth_reports", "reports")
         u_new, v_new = f["features"]
         d_cur, t_cur = f["current"]
         dev = next((t.device for t in d_cur if t is not None), torch.device("cuda", self.est._device))
-        ns = [int(t.numel()) for t in d_cur]
-        caps = [min(int(capacity[s]), ns[s]) if capacity is not None else ns[s] for s in range(self.S)]
+        caps = _capacities(capacity, [int(t.numel()) for t in d_cur], clamp=True)
         out = {"report": torch.empty((self.S, DepthReports.WORDS), dtype=torch.int64, device=dev),
                "points": [torch.empty((m, 3), dtype=torch.float64, device=dev) for m in caps] if points else None,
                "feature": [torch.empty(m, dtype=torch.int32, device=dev) for m in caps] if points else None}
         self.est._after_torch(*d_cur[:1])
-        self.depth_reports.collect_tracks(u_new, v_new, d_cur, t_cur, out["report"], caps if points else None,
-                                          out["points"], out["feature"])
+        reports.collect_tracks(u_new, v_new, d_cur, t_cur, out["report"], caps if points else None, out["points"], out["feature"])
         self.est.orderTorchAfter()
         return out
 
     def attach_traces(self) -> FeatureTraces:
         """The per-feature traces of the S sequences that traces() runs, for up to max_tracks tracks per sequence.  It
         takes the estimator's parameters as they are now."""
-        if self.feature_traces is None:
-            self.feature_traces = FeatureTraces(self.est, self.S, self.max_tracks)
-        return self.feature_traces
+        return self._attach("feature_traces")
 
     def traces(self, f, clouds, list_capacity: int = 0, planes: bool = True):
         """Why the tracks of table `f` (prepare_step() / prepare()) got their depths on this frame's clouds:
@@ -1288,31 +1204,28 @@ class TrackletBatch:
         synchronisation: torch's current stream is made to wait for the call; a host read synchronises as usual.
         attach_traces() first."""
         import torch
-        if self.feature_traces is None:
-            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.traces without attach_traces")
+        traces = self._attached("feature_traces", "traces")
         if clouds.get("cam") is None or clouds.get("pixel_map") is None:
             raise ValueError("clouds: projected_clouds(cam=True, pixel_map=True) of this frame")
         u_new, v_new = f["features"]
         dev = next((t.device for t in u_new if t is not None), torch.device("cuda", self.est._device))
-        ns = [int(t.numel()) if t is not None else 0 for t in u_new]
+        ns = [_entries(t) for t in u_new]
         cap = int(list_capacity)
         names = ("nb", "seg", "road", "road_inl")
         out = {"trace": [torch.empty((n, FeatureTraces.WORDS), dtype=torch.int64, device=dev) for n in ns]}
         for name in names:
             out[name] = [torch.empty((n, cap), dtype=torch.int32, device=dev) for n in ns] if cap else None
         self.est._after_torch(*[t for t in u_new if t is not None][:1])
-        self.feature_traces.collect_tracks(u_new, v_new, clouds["pixel_map"], clouds["index"], clouds["cam"], out["trace"],
-                                           f["coeffs"] if planes else None, list(f["keep"][1]) if planes else None, cap,
-                                           *[out[name] for name in names])
+        traces.collect_tracks(u_new, v_new, clouds["pixel_map"], clouds["index"], clouds["cam"], out["trace"],
+                              f["coeffs"] if planes else None, list(f["keep"][1]) if planes else None, cap,
+                              *[out[name] for name in names])
         self.est.orderTorchAfter()
         return out
 
     def attach_coverage(self) -> CoverageMaps:
         """The coverage maps of the S sequences that coverage() runs.  It takes the estimator's parameters as they are
         now."""
-        if self.coverage_maps is None:
-            self.coverage_maps = CoverageMaps(self.est, self.S)
-        return self.coverage_maps
+        return self._attach("coverage_maps")
 
     def coverage(self, clouds, coeffs=None, masks=None, maps=CoverageMaps.MAPS, bucket=None, capacity=None):
         """Where a feature of this frame can get a depth: CoverageMaps.collect on `clouds`, the dict
@@ -1325,11 +1238,9 @@ class TrackletBatch:
         torch's current stream is made to wait for the call; a host read synchronises as usual.  attach_coverage()
         first."""
         import torch
-        if self.coverage_maps is None:
-            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.coverage without attach_coverage")
+        cm = self._attached("coverage_maps", "coverage")
         if clouds.get("cam") is None or clouds.get("pixel_map") is None:
             raise ValueError("clouds: projected_clouds(cam=True, pixel_map=True) of this frame")
-        cm = self.coverage_maps
         unknown = [m for m in maps if m not in CoverageMaps.MAPS]
         if unknown:
             raise ValueError(f"maps: unknown {unknown}")
@@ -1338,8 +1249,7 @@ class TrackletBatch:
         for name in CoverageMaps.MAPS:
             out[name] = [torch.empty((cm.height, cm.width), dtype=torch.uint8, device=dev) for _ in range(self.S)] if name in maps else None
         if bucket is not None:
-            nb = cm.buckets(*bucket)
-            caps = [min(int(capacity[s]), nb) if capacity is not None else nb for s in range(self.S)]
+            caps = _capacities(capacity, [cm.buckets(*bucket)] * self.S, clamp=True)
             out["buckets"] = [torch.empty((m, 3), dtype=torch.int32, device=dev) for m in caps]
         self.est._after_torch(clouds["pixel_map"][0])
         cm.collect(clouds["pixel_map"], clouds["index"], clouds["cam"], out["record"], coeffs, masks,
@@ -1349,40 +1259,42 @@ class TrackletBatch:
 
     def attach_labels(self) -> SemanticLabels:
         """The label assignment of the S sequences that labels() queues behind a step."""
-        if self.semantic_labels is None:
-            self.semantic_labels = SemanticLabels(self.est, self.S)
-        return self.semantic_labels
+        return self._attach("semantic_labels")
 
     def labels(self, f, images, roi, label_out, votes_out=None):
         """The labels of the tracks of table `f` (prepare_step() / prepare()), queued on the estimator's stream - behind
         the step() / run() of `f` when called after it: SemanticLabels.assign on the table's u_new / v_new.
         attach_labels() first."""
-        if self.semantic_labels is None:
-            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.labels without attach_labels")
+        labels = self._attached("semantic_labels", "labels")
         u_new, v_new = f["features"]
-        self.semantic_labels.assign(images, roi, u_new, v_new, label_out, votes_out)
+        labels.assign(images, roi, u_new, v_new, label_out, votes_out)
 
     def attach_store(self, max_history: int) -> TrackletStore:
         """The GPU-resident tracklet maps of the S sequences that step() works on."""
-        if self.store is None:
-            self.store = TrackletStore(self.est, self.S, self.max_tracks, max_history)
-        return self.store
+        return self._attach("store", max_history)
+
+    def _tables(self, clouds, coeffs, masks, t_cur, t_last, nt, **lists):
+        """The table of a frame for step() / run(): a pointer table for clouds, masks and every list of `lists` under
+        its name (S tensors each, none of them None), the point counts "n", the track counts "nt" (lengths of `nt`), the
+        optional type tables, and what keeps the tensors alive: "keep" = clouds, masks, the lists in their order, t_cur,
+        t_last."""
+        S = self.S
+        vp = lambda ts: (C.c_void_p * S)(*[int(t.data_ptr()) for t in ts])  # noqa: E731
+        f = {"clouds": vp(clouds), "n": (C.c_int64 * S)(*[int(c.shape[0]) for c in clouds]),
+             "coeffs": np.ascontiguousarray(coeffs, dtype=np.float32).reshape(S, 4), "masks": vp(masks),
+             "nt": (C.c_int64 * S)(*[int(t.shape[0]) for t in nt]),
+             "t_cur": vp(t_cur) if t_cur is not None else None, "t_last": vp(t_last) if t_last is not None else None}
+        f.update((name, vp(ts)) for name, ts in lists.items())
+        f["keep"] = (list(clouds), list(masks), *[list(ts) for ts in lists.values()], t_cur, t_last)
+        f["features"] = (list(lists["u_new"]), list(lists["v_new"]))
+        f["current"] = (list(lists["d_cur"]), list(t_cur) if t_cur is not None else None)
+        return f
 
     def prepare_step(self, clouds, coeffs, masks, ids, u_new, v_new, u_old, v_old, d_cur, d_last, t_cur=None, t_last=None):
         """Pointer tables of one frame of every sequence for step(): as prepare(), with the S int32 CUDA tensors of
         track ids in place of the new-track masks."""
-        S = self.S
-        vp = lambda ts: (C.c_void_p * S)(*[int(t.data_ptr()) for t in ts])  # noqa: E731
-        co = np.ascontiguousarray(coeffs, dtype=np.float32).reshape(S, 4)
-        return {"clouds": vp(clouds), "n": (C.c_int64 * S)(*[int(c.shape[0]) for c in clouds]), "coeffs": co,
-                "masks": vp(masks), "ids": vp(ids), "u_new": vp(u_new), "v_new": vp(v_new), "u_old": vp(u_old),
-                "v_old": vp(v_old), "nt": (C.c_int64 * S)(*[int(t.shape[0]) for t in ids]), "d_cur": vp(d_cur),
-                "d_last": vp(d_last), "t_cur": vp(t_cur) if t_cur is not None else None,
-                "t_last": vp(t_last) if t_last is not None else None,
-                "keep": (list(clouds), list(masks), list(ids), list(u_new), list(v_new), list(u_old), list(v_old),
-                         list(d_cur), list(d_last), t_cur, t_last),
-                "features": (list(u_new), list(v_new)),
-                "current": (list(d_cur), list(t_cur) if t_cur is not None else None)}
+        return self._tables(clouds, coeffs, masks, t_cur, t_last, ids, ids=ids, u_new=u_new, v_new=v_new, u_old=u_old,
+                            v_old=v_old, d_cur=d_cur, d_last=d_last)
 
     def step(self, f, nxt: Optional["TrackletBatch"] = None, handover: str = "projection", restart=None, leaving=None):
         """run() with the tracklet maps on the GPU (mld_tracklets_step_device): projection of the current bank, then
@@ -1393,24 +1305,19 @@ class TrackletBatch:
         leaving: None, or the buffers of store.set_leaving_sink() as a dict (store.leaving_buffers() makes one) - they
         receive what this step removes from the store: a restarting lane's tracks whole, of the other lanes the tracks
         that end and the entries that fall off (store.export_leaving)."""
-        if self.store is None:
-            raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED, "TrackletBatch.step without attach_store")
-        S, est, lib = self.S, self.est, self.est._lib
+        store = self._attached("store", "step")
+        est, lib = self.est, self.est._lib
         uniform, last, again = self._lane_flags(restart)
         if leaving is not None:
-            self.store.set_leaving_sink(**{k: leaving[k] for k in TrackletStore.LEAVING_KEYS + ("record",)})
+            store.set_leaving_sink(**{k: leaving[k] for k in TrackletStore.LEAVING_KEYS + ("record",)})
         self._project(f, last)
-        if nxt is not None and nxt is not self:
-            if handover == "classify":
-                nxt.est.orderAfterClassify(est)
-            else:
-                nxt.est.orderAfter(est)
+        self._release(nxt, handover)
         tail = (f["ids"], f["u_new"], f["v_new"], f["u_old"], f["v_old"], f["nt"], f["d_cur"], f["d_last"], f["t_cur"], f["t_last"])
         if last is None:
-            rc = lib.mld_tracklets_step_device(est._ctx, self.store._tr, self.bank, 1 if uniform else 0, *tail)
+            rc = lib.mld_tracklets_step_device(est._ctx, store._tr, self.bank, 1 if uniform else 0, *tail)
         else:
-            rc = lib.mld_tracklets_step_lanes_device(est._ctx, self.store._tr, self.bank, last, again, *tail)
-        self.store._check(rc)
+            rc = lib.mld_tracklets_step_lanes_device(est._ctx, store._tr, self.bank, last, again, *tail)
+        store._check(rc)
         self._stepped(f)
 
     def prepare(self, clouds, coeffs, masks, u_new, v_new, u_old, v_old, is_new, d_cur, d_last, t_cur=None, t_last=None):
@@ -1418,18 +1325,8 @@ class TrackletBatch:
         clouds / masks: S torch CUDA tensors ([N,4] float32 / int32 inlier bitmask), coeffs [S,4] float32 (host);
         u_new ... is_new: S CUDA tensors each (float32 x4, uint8); outputs: S CUDA float32 tensors (d_cur, d_last) and
         optional int32 (t_cur, t_last)."""
-        S = self.S
-        vp = lambda ts: (C.c_void_p * S)(*[int(t.data_ptr()) for t in ts])  # noqa: E731
-        co = np.ascontiguousarray(coeffs, dtype=np.float32).reshape(S, 4)
-        return {"clouds": vp(clouds), "n": (C.c_int64 * S)(*[int(c.shape[0]) for c in clouds]), "coeffs": co,
-                "masks": vp(masks), "u_new": vp(u_new), "v_new": vp(v_new), "u_old": vp(u_old), "v_old": vp(v_old),
-                "is_new": vp(is_new), "nt": (C.c_int64 * S)(*[int(t.shape[0]) for t in u_new]), "d_cur": vp(d_cur),
-                "d_last": vp(d_last), "t_cur": vp(t_cur) if t_cur is not None else None,
-                "t_last": vp(t_last) if t_last is not None else None,
-                "keep": (list(clouds), list(masks), list(u_new), list(v_new), list(u_old), list(v_old), list(is_new),
-                         list(d_cur), list(d_last), t_cur, t_last),
-                "features": (list(u_new), list(v_new)),
-                "current": (list(d_cur), list(t_cur) if t_cur is not None else None)}
+        return self._tables(clouds, coeffs, masks, t_cur, t_last, u_new, u_new=u_new, v_new=v_new, u_old=u_old, v_old=v_old,
+                            is_new=is_new, d_cur=d_cur, d_last=d_last)
 
     def run(self, f, nxt: Optional["TrackletBatch"] = None, handover: str = "projection", restart=None):
         """One frame of every sequence from prepared tables: projection of the current bank, then the tracklet call.
@@ -1440,12 +1337,7 @@ class TrackletBatch:
         S, est, lib = self.S, self.est, self.est._lib
         uniform, last, _ = self._lane_flags(restart)
         self._project(f, last)
-        if nxt is not None and nxt is not self:
-            # (released at the end of this projection, or behind this step's classification kernel: include/mld.h)
-            if handover == "classify":
-                nxt.est.orderAfterClassify(est)
-            else:
-                nxt.est.orderAfter(est)
+        self._release(nxt, handover)
         tail = (f["u_new"], f["v_new"], f["u_old"], f["v_old"], f["is_new"], f["nt"], f["d_cur"], f["d_last"], f["t_cur"], f["t_last"])
         if last is None:
             est._check(lib.mld_tracklets_depths_device(est._ctx, S, self.bank, 1 if uniform else 0, *tail))
@@ -1458,31 +1350,8 @@ class TrackletBatch:
         self.run(self.prepare(clouds, *args, **kw))
 
     def close(self):
-        if self.semantic_labels is not None:
-            self.semantic_labels.close()
-            self.semantic_labels = None
-        if self.store is not None:
-            self.store.close()
-            self.store = None
-        if self.planes is not None:
-            self.planes.close()
-            self.planes = None
-        if self.rplanes is not None:
-            self.rplanes.close()
-            self.rplanes = None
-        if self.pclouds is not None:
-            self.pclouds.close()
-            self.pclouds = None
-        if self.depth_reports is not None:
-            self.depth_reports.close()
-            self.depth_reports = None
-        if self.inliers is not None:
-            self.inliers.close()
-            self.inliers = None
-        if self.feature_traces is not None:
-            self.feature_traces.close()
-            self.feature_traces = None
-        if self.coverage_maps is not None:
-            self.coverage_maps.close()
-            self.coverage_maps = None
+        for attr in self._ATTACHABLE:
+            if getattr(self, attr) is not None:
+                getattr(self, attr).close()
+                setattr(self, attr, None)
         self.est.close()
