@@ -1341,6 +1341,94 @@ int mld_coverage_maps_collect_device(mld_coverage_maps* cm, const int32_t* const
                                      const int64_t* bucket_capacity, int32_t* const* bucket_out);
 
 /*
+ * Depth images of a batch — the depth path at every pixel of a grid over the camera image, for n_seq independent sequences
+ * in one call: what a depth call answers for a feature, answered for every pixel, or every n-th pixel, in GPU memory.  No
+ * frame slot, no uv array, no synchronisation.  Every grid pixel gets the full per-feature path (SURVEY.md 8(a), rows B1 to
+ * B10): the narrow window by the f64 rule of mld_coverage_maps (never x +- const), the histogram segmentation with all its
+ * early returns, the max-spanning triangle or the first three points, the planarity test, the viewing ray with its flip,
+ * Hyperplane::Through with the orthogonality test, the global and local thresholds and cut-behind-camera; and the road
+ * fallback: the wide window, the f32 far test after the f64 camera->lidar transform, the mask bit of the original index,
+ * the M-estimator fit (its weighted sums taken about the list's first point), the `Normal` intersection, the thresholds,
+ * type 16.  Types are the reference's, main-path depths are bit for bit the depth calls', road depths agree to the road
+ * tolerance of the project (1e-4 m).
+ *
+ * Inputs: map[s], index[s], index_len[s], cam[s], n_points[s], coeffs and mask_dev as mld_coverage_maps_collect_device takes
+ * them, with the same meaning and the same bad-input rule: a map value other than -1 outside [0, index_len[s]) and an index
+ * value outside [0, n_points[s]) make the cell EMPTY and - when a window that is scanned meets the cell - set
+ * MLD_DEPTH_IMAGE_FLAG_BAD_INPUT in the sequence's record; no read leaves the arrays as the host tables size them.  A
+ * sequence without a plane - mask_dev[s] NULL, or coeffs NULL, or do_use_ransac_plane off - has no road fallback.
+ *
+ * Grid: grid pixel (i, j), 0 <= i < grid_w, 0 <= j < grid_h, stands for the feature ((double)(x0 + i * step_x),
+ * (double)(y0 + j * step_y)); its outputs have the index i + j * grid_w.  The grid lies inside the image and the steps are
+ * >= 1: otherwise MLD_ERR_INVALID_ARG with a text naming the argument.
+ *
+ * Outputs, grid_w * grid_h entries each; every table and every entry is optional; each one asked for is written exactly
+ * once and nothing outside it is touched:
+ *   type_out     uint8: the DepthResultType
+ *   depth_out    f64 (8-byte aligned): the path's depth, -1 on every failure, as the depth calls return it
+ *   depth32_out  f32 (4-byte aligned): (float) of that value, the precision FeaturePoint.d carries
+ * record_out_dev: n_seq records (DEVICE memory, 8-byte aligned), every one written completely on every call.
+ *
+ * mld_depth_images_create: an object bound to `ctx` (its stream, its device) for calls of n_seq (1 .. 65536) sequences.
+ *   params, camera and T_cam_lidar (row-major 3x4) are copied: pass the values the context was created with.  All memory
+ *   is allocated here, none per call; with TILES = ceil(W / 64) * ceil(H / 16), the tiles of the full grid:
+ *     device  120 * n_seq bytes                 (the descriptors)
+ *             128 * TILES * n_seq bytes         (overflow words: four 64-bit words per wavefront, four wavefronts per tile)
+ *             512 * TILES * n_seq bytes         (partial counts of the record: 32 int32 per wavefront)
+ *     pinned  16 * 120 * n_seq bytes            (the descriptor ring)
+ *   Judged in this order, the context LAST and nothing of it used before: the size; params, camera and T_cam_lidar (null:
+ *   MLD_ERR_INVALID_ARG); then
+ *     MLD_ERR_UNSUPPORTED_MODE  do_use_PCA (the eigen-solve is a tolerance path), plane_estimator_use_triangle_maximation
+ *                               (the triangle road estimator is a rare path) and set_all_depths_to_zero (the depth calls
+ *                               answer it without a kernel), in this order
+ *     the refusals of mld_create for a parameter set, an image size, intrinsics and a transform, with its status codes
+ *     MLD_ERR_CAPACITY          a wide window that can cover more than 1024 cells, counted as mld_feature_traces counts it
+ *     MLD_ERR_CAPACITY          n_seq sequences of an image that need more than 2^31 - 1 blocks
+ *     MLD_ERR_INVALID_ARG       a null context
+ *   Returns NULL on failure with the reason in *status_out (optional) and the text in
+ *   mld_depth_images_last_error(NULL).  Destroy the object before its context.
+ *
+ * mld_depth_images_render_device: HOST tables of n_seq entries, consumed before the call returns; every array they name is
+ * DEVICE memory.  Asynchronous on the context's stream: no synchronisation, no host read of device data, no runtime call per
+ *   sequence, nothing allocated per call, no atomics, four launches: the descriptor upload, k_depth_image_lane (one lane
+ *   per grid pixel over tiles of 64 x 16 grid pixels whose map cells, halo included, are staged in LDS once; type-2 pixels
+ *   leave on the count alone; lists of up to 32 entries per lane), k_depth_image_coop (one wavefront per pixel whose narrow
+ *   list or whose list of road inliers is longer than 32 entries; lists up to the 1024-cell bound) and
+ *   k_depth_image_finish (the record from per-wavefront partial counts).  Which route a pixel takes changes no output
+ *   beyond the road tolerance and no type.  The device arrays must stay valid until the work has run.  Like a context, the
+ *   object serves one call at a time.
+ *   MLD_ERR_INVALID_ARG with a text naming the function and the argument (mld_depth_images_last_error; "null object (di)"
+ *   of NULL for a null object) on: a null object, a null table map, index, index_len, cam or n_points, a null or
+ *   misaligned record_out_dev, coeffs without mask_dev or the other way round, step_x or step_y below 1, grid_w or grid_h
+ *   below 1, x0 or y0 outside the image, a last column or row outside the image, a negative count, a null map array
+ *   (index, cam: where index_len[s], n_points[s] > 0), an int32 or f32 array that is not 4-byte aligned, an f64 array that is
+ *   not 8-byte aligned.  MLD_ERR_CAPACITY on n_points[s] or index_len[s] beyond 8 388 607.
+ * In libmld_hip_ab.so only, MLD_DEPTH_IMAGE_COOP=1 in the environment, read at create, sends every pixel that clears the
+ * neighbour test through k_depth_image_coop.
+ */
+enum { MLD_DEPTH_IMAGE_FLAG_BAD_INPUT = 1, MLD_DEPTH_IMAGE_FLAG_HAS_PLANE = 2 };
+
+typedef struct mld_depth_image_record {    /* 200 bytes, 8-byte aligned */
+    int64_t counts[MLD_RESULT_TYPE_COUNT];  /* pixels of every DepthResultType */
+    int64_t n_pixels;       /* grid_w * grid_h */
+    int64_t n_depth;        /* pixels with depth >= 0 */
+    int64_t n_cooperative;  /* pixels that left the lane-per-pixel route for k_depth_image_coop */
+    int32_t flags;          /* MLD_DEPTH_IMAGE_FLAG_* */
+    int32_t pad_;
+} mld_depth_image_record;
+
+typedef struct mld_depth_images mld_depth_images;
+mld_depth_images* mld_depth_images_create(mld_ctx* ctx, int n_seq, const mld_params* params, const mld_camera* camera,
+                                          const double T_cam_lidar[12], int* status_out);
+void mld_depth_images_destroy(mld_depth_images* di);
+const char* mld_depth_images_last_error(const mld_depth_images* di);
+int mld_depth_images_render_device(mld_depth_images* di, const int32_t* const* map, const int32_t* const* index,
+                                   const int64_t* index_len, const double* const* cam, const int64_t* n_points,
+                                   const float* coeffs, const uint32_t* const* mask_dev, int x0, int y0, int step_x, int step_y,
+                                   int grid_w, int grid_h, double* const* depth_out, float* const* depth32_out,
+                                   uint8_t* const* type_out, mld_depth_image_record* record_out_dev);
+
+/*
  * Debug / parity getters (host buffers; each synchronises).
  *   mld_get_visible_count           -> _points_cs_image_visible.cols()         (DepthEstimator.cpp:192)
  *   mld_get_visible_image_points    -> getPointsCloudImageCs, 2 x Nvis col-major (:392-394)

@@ -181,6 +181,16 @@ class MldCoverageRecord(C.Structure):
                 ("pad_", C.c_int32 * 3)]
 
 
+# mld_depth_images: the bits of mld_depth_image_record::flags (include/mld.h)
+MLD_DEPTH_IMAGE_FLAG_BAD_INPUT, MLD_DEPTH_IMAGE_FLAG_HAS_PLANE = 1, 2
+
+
+class MldDepthImageRecord(C.Structure):
+    """mld_depth_image_record (include/mld.h): one sequence of mld_depth_images_render_device, 200 bytes = 25 int64."""
+    _fields_ = [("counts", C.c_int64 * 21), ("n_pixels", C.c_int64), ("n_depth", C.c_int64), ("n_cooperative", C.c_int64),
+                ("flags", C.c_int32), ("pad_", C.c_int32)]
+
+
 # Every symbol include/mld.h declares: (name, restype, argtypes)
 _P = C.POINTER
 _SIGNATURES = [
@@ -311,6 +321,12 @@ _SIGNATURES = [
     ("mld_coverage_maps_collect_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 2 + [_P(C.c_int64), _P(C.c_void_p),
                                                    _P(C.c_int64), _P(C.c_float)] + [_P(C.c_void_p)] * 6 +
      [C.c_void_p, C.c_int, C.c_int, _P(C.c_int64), _P(C.c_void_p)]),
+    ("mld_depth_images_create", C.c_void_p, [C.c_void_p, C.c_int, _P(MldParams), _P(MldCamera), _P(C.c_double), _P(C.c_int)]),
+    ("mld_depth_images_destroy", None, [C.c_void_p]),
+    ("mld_depth_images_last_error", C.c_char_p, [C.c_void_p]),
+    ("mld_depth_images_render_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 2 + [_P(C.c_int64), _P(C.c_void_p),
+                                                 _P(C.c_int64), _P(C.c_float), _P(C.c_void_p)] + [C.c_int] * 6 +
+     [_P(C.c_void_p)] * 3 + [C.c_void_p]),
     ("mld_get_visible_count", C.c_int, [C.c_void_p, C.c_int, _P(C.c_int64)]),
     ("mld_get_visible_image_points", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
     ("mld_get_point_index", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),

@@ -236,9 +236,9 @@ def _result_tensor(t, shape, size, name):
 
 class _BatchObject:
     """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes, ProjectedClouds, DepthReports, PlaneInliers,
-    FeatureTraces and CoverageMaps share: an object of the C-ABI (mld_<_NAME>_create / _destroy / _last_error) on an
-    estimator's context, its handle in the attribute named _HANDLE, the tensors of the calls that may still be queued,
-    and one copy of every argument check.  The helpers, here and above:
+    FeatureTraces, CoverageMaps and DepthImages share: an object of the C-ABI (mld_<_NAME>_create / _destroy /
+    _last_error) on an estimator's context, its handle in the attribute named _HANDLE, the tensors of the calls that may
+    still be queued, and one copy of every argument check.  The helpers, here and above:
 
     _calibration     the parameter, camera and transform arguments of _create
     _create, close   the object of the C-ABI; _check raises its last error for a status that is not MLD_OK
@@ -924,6 +924,72 @@ class CoverageMaps(_BatchObject):
         self._hold(pixel_map, index, cam, record, masks, *maps, bucket_out)
 
 
+class DepthImages(_BatchObject):
+    """Dense depth images for S sequences per call (mld_depth_images_*, include/mld.h): the depth path - narrow window,
+    histogram, triangle, thresholds, road fallback with its fit - at every pixel of a grid over the camera image: the
+    result type, the depth as float32 and optionally as float64, and per sequence a record of counts.  It runs on the
+    tensors ProjectedClouds.export wrote (pixel_map, index, cam) and on the planes as prepare() / prepare_step() take
+    them; it needs no frame slot and no feature array.  `parameters` (default: the estimator's) is copied at creation.
+    Lists of S torch CUDA tensors in and out; asynchronous on the estimator's stream.  Close it before its estimator."""
+
+    _NAME, _HANDLE = "depth_images", "_di"
+    WORDS = 25  # int64 words of a record (capi.MldDepthImageRecord, 200 bytes)
+    DTYPE = np.dtype(capi.MldDepthImageRecord)
+
+    def __init__(self, estimator: DepthEstimator, n_seq: int, parameters=None):
+        self.S = int(n_seq)
+        self._create(estimator, self.S, *self._calibration(estimator, "parameters", "camera", "transform", parameters=parameters))
+
+    @classmethod
+    def records(cls, record) -> np.ndarray:
+        """A record tensor (int64 [S, 25]) as a NumPy record array with the fields of capi.MldDepthImageRecord (copies
+        to the host, which synchronises as usual)."""
+        return np.ascontiguousarray(record.cpu().numpy()).reshape(-1).view(cls.DTYPE)
+
+    def grid(self, grid=None):
+        """(x0, y0, step_x, step_y, grid_w, grid_h) of `grid`: None (every pixel), (x0, y0, step_x, step_y) - as many
+        grid pixels as fit into the image from (x0, y0) on - or all six."""
+        if grid is None:
+            return 0, 0, 1, 1, self.width, self.height
+        g = [int(v) for v in grid]
+        if len(g) == 4:
+            x0, y0, sx, sy = g
+            if sx < 1 or sy < 1 or not (0 <= x0 < self.width and 0 <= y0 < self.height):
+                raise ValueError("grid: (x0, y0) inside the image and steps >= 1")
+            return x0, y0, sx, sy, (self.width - 1 - x0) // sx + 1, (self.height - 1 - y0) // sy + 1
+        if len(g) != 6:
+            raise ValueError("grid: None, (x0, y0, step_x, step_y) or (x0, y0, step_x, step_y, grid_w, grid_h)")
+        return tuple(g)
+
+    def render(self, pixel_map, index, cam, record, coeffs=None, masks=None, grid=None, depth=None, depth32=None, type=None):
+        """pixel_map, index, cam: the S tensors each that ProjectedClouds.export wrote for the clouds (int32 [height,
+        width], int32 of a capacity that did not truncate, float64 [points, 3]; index and cam entries may be None for an
+        empty cloud); record: an int64 CUDA tensor of at least 25 * S entries (a contiguous [S, 25]:
+        capi.MldDepthImageRecord, see records()); coeffs (float32 [S, 4], host) and masks (S int32 CUDA tensors, an entry
+        None: that sequence has no plane): both or neither; grid: see grid(); depth (float64), depth32 (float32), type
+        (uint8): None, or S CUDA tensors of at least grid_w * grid_h entries (a contiguous [grid_h, grid_w]; single
+        entries may be None)."""
+        cells = self.width * self.height
+        x0, y0, sx, sy, gw, gh = self.grid(grid)
+        n = max(gw, 0) * max(gh, 0)
+        self._lengths(pixel_map=pixel_map, index=index, cam=cam, masks=masks, depth=depth, depth32=depth32, type=type)
+        planes = self._plane_args(coeffs, masks)
+        _holds(record, "*", self.WORDS * self.S, 8, "record", required=True)
+        for s in range(self.S):
+            _holds(pixel_map[s], s, cells, 4, "pixel_map", required=True)
+            _holds(index[s], s, 0, 4, "index")
+            _holds(cam[s], s, 0, 8, "cam")
+            _holds(_at(depth, s), s, n, 8, "depth")
+            _holds(_at(depth32, s), s, n, 4, "depth32")
+            _holds(_at(type, s), s, n, 1, "type")
+        vp, opt = self._ptrs, self._opt
+        self._check(self._lib.mld_depth_images_render_device(
+            self._di, vp(pixel_map), vp(index), self._i64(_entries(t) for t in index), vp(cam),
+            self._i64(_entries(t, 3) for t in cam), *planes, x0, y0, sx, sy, gw, gh, opt(depth), opt(depth32), opt(type),
+            int(record.data_ptr())))
+        self._hold(pixel_map, index, cam, record, masks, depth, depth32, type)
+
+
 class TrackletBatch:
     """The tracklet layer for S independent sequences at once (mld_set_clouds_planes_range_device +
     mld_tracklets_depths_device): the estimator's frame slots are two banks of S slots, sequence s keeps its current
@@ -948,7 +1014,8 @@ class TrackletBatch:
                    "depth_reports": (DepthReports, "attach_reports", ("max_tracks",)),
                    "inliers": (PlaneInliers, "attach_plane_inliers", ()),
                    "feature_traces": (FeatureTraces, "attach_traces", ("max_tracks",)),
-                   "coverage_maps": (CoverageMaps, "attach_coverage", ())}
+                   "coverage_maps": (CoverageMaps, "attach_coverage", ()),
+                   "depth_image_maps": (DepthImages, "attach_depth_images", ())}
 
     def __init__(self, parameters, camera: CameraPinhole, transform_lidar_to_cam, n_seq: int, max_tracks: int,
                  device: int = 0, list_capacity=None):
@@ -969,14 +1036,14 @@ class TrackletBatch:
 
     def _attach(self, attr, *args):
         """The object of `attr`, made on the first call from (estimator, S, the table's attributes, *args)."""
-        if getattr(self, attr) is None:
+        if getattr(self, attr, None) is None:
             cls, _, own = self._ATTACHABLE[attr]
             setattr(self, attr, cls(self.est, self.S, *[getattr(self, a) for a in own], *args))
         return getattr(self, attr)
 
     def _attached(self, attr, method):
         """The object of `attr` for `method`, which cannot run without it."""
-        obj = getattr(self, attr)
+        obj = getattr(self, attr, None)
         if obj is None:
             raise DepthEstimatorError(capi.MLD_ERR_NOT_INITIALIZED,
                                       f"TrackletBatch.{method} without {self._ATTACHABLE[attr][1]}")
@@ -1257,6 +1324,35 @@ class TrackletBatch:
         self.est.orderTorchAfter()
         return out
 
+    def attach_depth_images(self) -> DepthImages:
+        """The depth images of the S sequences that depth_images() runs.  It takes the estimator's parameters as they
+        are now."""
+        return self._attach("depth_image_maps")
+
+    def depth_images(self, clouds, coeffs=None, masks=None, grid=None, f64=False):
+        """The depth path at every pixel of a grid over this frame's image: DepthImages.render on `clouds`, the dict
+        projected_clouds(cam=True, pixel_map=True) returned for this frame's clouds with a capacity that did not
+        truncate, and on the planes as prepare() / prepare_step() take them (coeffs float32 [S, 4] on the host, masks S
+        int32 CUDA tensors; both None: without planes).  grid: None (every pixel), (x0, y0, step_x, step_y) or all six
+        of DepthImages.grid().  Returns a dict with record (int64 [S, 25]: capi.MldDepthImageRecord, see
+        DepthImages.records()), type (S uint8 [grid_h, grid_w]), depth32 (S float32 [grid_h, grid_w]) and depth (S
+        float64 [grid_h, grid_w] with f64, else None).  No synchronisation: torch's current stream is made to wait for
+        the call; a host read synchronises as usual.  attach_depth_images() first."""
+        import torch
+        di = self._attached("depth_image_maps", "depth_images")
+        if clouds.get("cam") is None or clouds.get("pixel_map") is None:
+            raise ValueError("clouds: projected_clouds(cam=True, pixel_map=True) of this frame")
+        g = di.grid(grid)
+        dev = clouds["pixel_map"][0].device
+        make = lambda dtype: [torch.empty((g[5], g[4]), dtype=dtype, device=dev) for _ in range(self.S)]
+        out = {"record": torch.empty((self.S, DepthImages.WORDS), dtype=torch.int64, device=dev), "type": make(torch.uint8),
+               "depth32": make(torch.float32), "depth": make(torch.float64) if f64 else None}
+        self.est._after_torch(clouds["pixel_map"][0])
+        di.render(clouds["pixel_map"], clouds["index"], clouds["cam"], out["record"], coeffs, masks, grid=g, depth=out["depth"],
+                  depth32=out["depth32"], type=out["type"])
+        self.est.orderTorchAfter()
+        return out
+
     def attach_labels(self) -> SemanticLabels:
         """The label assignment of the S sequences that labels() queues behind a step."""
         return self._attach("semantic_labels")
@@ -1351,7 +1447,7 @@ class TrackletBatch:
 
     def close(self):
         for attr in self._ATTACHABLE:
-            if getattr(self, attr) is not None:
+            if getattr(self, attr, None) is not None:
                 getattr(self, attr).close()
                 setattr(self, attr, None)
         self.est.close()
