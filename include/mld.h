@@ -1429,6 +1429,127 @@ int mld_depth_images_render_device(mld_depth_images* di, const int32_t* const* m
                                    uint8_t* const* type_out, mld_depth_image_record* record_out_dev);
 
 /*
+ * Region depths of a batch — the foreground depth of image RECTANGLES (a detector's 2-D box, a label blob's bounding box,
+ * a tile of a matching prior), for n_seq independent sequences in one call.  A box is scanned like the window of
+ * NeighborFinderPixel::getNeighbors (NeighborFinderPixel.cpp:70-79) with the box's own integer edges, of
+ * ANY size, and its points go through the first-local-maximum histogram of PointHistogram::FilterPointsMinDistBlob
+ * (HistogramPointDepth.cpp:30-100, row B3).  Besides the histogram's bin the record holds the count, the smallest, the
+ * largest and the EXACT median depth and the nearest point.  Optionally the points of a ground plane are left out, so that
+ * the road under a car does not answer for the car.  No frame slot, no synchronisation; the record holds only counts, order
+ * statistics and bin borders, so the output does not depend on the order in which the GPU meets the points.
+ *
+ * Inputs: map[s], index[s], index_len[s], cam[s] and n_points[s] are the arrays mld_projected_clouds_export_device writes,
+ * with the same meaning and the same bad-input rule as in the other objects that read them: a map value other than -1
+ * outside [0, index_len[s]) and an index value outside [0, n_points[s]) make the cell EMPTY and set
+ * MLD_REGION_FLAG_BAD_INPUT in the record of every box that contains the cell; no read leaves the arrays as the host tables
+ * size them.  The depth of an occupied cell is the camera-frame z of its point, cam[s][3 * index[s][map value] + 2].  A z
+ * that is not > 0 (zero, negative, NaN) is bad input too: the point is skipped and the flag is set.
+ * mask_dev (optional table, optional entries): mask_dev[s] is the plane's inlier bitmask over the ORIGINAL point index, as
+ * mld_semantic_planes_estimate_device and mld_ransac_planes_estimate_device write it (ceil(n_points[s] / 32) words).  A
+ * point whose bit is set is excluded and counted in n_ground.  NULL: that sequence excludes nothing.
+ * boxes[s]: n_boxes[s] x 4 int32 (x0, y0, x1, y1), both corners inclusive, 0 <= n_boxes[s] <= max_boxes (DEVICE memory; NULL
+ * with n_boxes[s] == 0).  A box is clipped to [0, W - 1] x [0, H - 1]; the rows and columns scanned are those of
+ * NeighborFinderPixel.cpp:70-79 for the same edges.  A box with x1 < x0 or y1 < y0, or one that the clipping leaves nothing
+ * of, is EMPTY.
+ * record_out[s]: n_boxes[s] records (DEVICE memory, 8-byte aligned; NULL with n_boxes[s] == 0), record b for box b, every one
+ * written completely on every call and nothing else touched.
+ *
+ * The record.  "Counted points" are the occupied cells of the clipped box with z > 0 whose mask bit is not set.
+ *   n_points      counted points
+ *   n_ground      points with z > 0 that the mask excluded
+ *   n_seg         counted points with hist_lower <= z < hist_higher; 0 without a bin
+ *   flags         MLD_REGION_FLAG_BAD_INPUT 1, _EMPTY_BOX 2, _HIST_FOUND 4, _HIST_CAPPED 8, _HAS_MASK 16 (the sequence has a
+ *                 mask, whatever the box holds)
+ *   nearest_orig  the original index of the counted point with the smallest z; among equal z the first in row-major scan
+ *                 order (rows from the top, columns from the left); -1 without a counted point
+ *   clip          the clipped box (x0, y0, x1, y1); all -1 for an EMPTY box
+ *   z_min, z_max, z_median   over the z of the counted points.  z_median is the element of rank (n_points - 1) / 2 (0-based,
+ *                 integer division) in ascending order: an element of the set, never an interpolation.  All three are -1
+ *                 with n_points == 0.
+ *   hist_lower, hist_higher  the borders FilterPointsMinDistBlob returns for the z of the counted points with
+ *                 histogram_segmentation_bin_witdh and histogram_segmentation_min_pointcount, every quirk kept: `int maxDist`
+ *                 from ceil, binCount = (int)(maxDist / binWidth + 1), binCount <= 1 fails, the bin index of
+ *                 Histogram::AddElement ((int)min(|min(z, 1e10) / binWidth|, binCount - 1)), the first bin that reaches the
+ *                 minimal count and exceeds every earlier one, the scan ends at the first bin that decreases, and a bin of
+ *                 zero points behind a bin with points fails the whole rule.  -1 / -1 when the rule returns false.  (The
+ *                 depth path clamps z to 999 m before this rule, DepthEstimator.cpp:743; here z is taken as it is.  Where the
+ *                 reference converts a double beyond the int range - a z or a bin count of 2^31 and more - the values
+ *                 saturate at 2^31 - 1.)
+ * Histogram storage: the histogram is kept relative to the bin of z_min, MLD_REGION_HIST_BINS bins long.  If the rule would
+ * have to look at a bin beyond them - a run of bins that never decreases and never empties over more than
+ * MLD_REGION_HIST_BINS * binWidth metres - the record gets MLD_REGION_FLAG_HIST_CAPPED and no bin (borders -1, n_seg 0, no
+ * HIST_FOUND); nothing else of the record changes.
+ *
+ * mld_region_depths_create: an object bound to `ctx` (its stream, its device) for calls of n_seq (1 .. 65536) sequences of
+ *   up to max_boxes (>= 1) boxes each.  Of params only histogram_segmentation_bin_witdh and
+ *   histogram_segmentation_min_pointcount are read, of camera only width and height; both are copied.  All memory is
+ *   allocated here, none per call:
+ *     device  64 * n_seq bytes        (the descriptors)
+ *     pinned  16 * 64 * n_seq bytes   (the descriptor ring)
+ *   Judged in this order, the context LAST and nothing of it used before: n_seq and max_boxes; params and camera (null:
+ *   MLD_ERR_INVALID_ARG); then
+ *     MLD_ERR_INVALID_ARG   a bin width that is not finite or not > 0; an image size below 1 x 1
+ *     MLD_ERR_CAPACITY      an image larger than 65535 pixels on a side or 2^30 pixels in all
+ *     MLD_ERR_CAPACITY      n_seq * max_boxes beyond 2^31 - 1 (blocks of a launch)
+ *     MLD_ERR_INVALID_ARG   a null context
+ *   Returns NULL on failure with the reason in *status_out (optional) and the text in
+ *   mld_region_depths_last_error(NULL).  Destroy the object before its context.
+ *
+ * mld_region_depths_collect_device: HOST tables of n_seq entries, consumed before the call returns; every array they name is
+ * DEVICE memory.  Asynchronous on the context's stream: no synchronisation, no host read of device data, no runtime call per
+ *   sequence, nothing allocated per call, no global atomics, no floating-point accumulation, two launches: the descriptor
+ *   upload and k_region_depths, ONE BLOCK PER BOX (256 threads; a call's grid is n_seq times its largest n_boxes[s]; a call
+ *   without a box launches nothing).  The block walks the rows of the clipped box with coalesced loads of the map, eight
+ *   cells per thread in flight, gathers index, z and the mask bit, and reduces count, minimum, maximum and nearest point.
+ *   A box of up to MLD_REGION_LIST_CAPACITY counted points keeps their z in LDS and takes the histogram, n_seg and the
+ *   median from that list; a larger box scans its cells again for the histogram and for n_seg, and for the median until the
+ *   values still in question fit the list.  The median is selected in both routes by the same radix passes of 8 bits over
+ *   the bit pattern of z (positive doubles order as their bit patterns), from the highest bit in which z_min and z_max
+ *   differ downwards, so the record is the same bit for bit on either route.  The work
+ *   of a block follows the cells of its box: a box without a counted point leaves after the first scan, a box of one value
+ *   needs no radix pass.  The device arrays must stay valid until the work has run.  Like a context, the object serves one
+ *   call at a time.
+ *   MLD_ERR_INVALID_ARG with a text naming the function and the argument (mld_region_depths_last_error; "null object (rd)"
+ *   of NULL for a null object) on: a null object, a null table map, index, index_len, cam, n_points, boxes, n_boxes or
+ *   record_out, a negative count, n_boxes[s] beyond max_boxes, a null map array (index, cam: where index_len[s],
+ *   n_points[s] > 0; boxes, record_out: where n_boxes[s] > 0), an int32 array that is not 4-byte aligned, an f64 or record
+ *   array that is not 8-byte aligned.  MLD_ERR_CAPACITY on n_points[s] or index_len[s] beyond 8 388 607.
+ * In libmld_hip_ab.so only, MLD_REGION_LIST_CAPACITY=<n> in the environment (0 .. 2048), read at create, sets the capacity
+ * of the list: 0 sends every box through the re-scanning route.
+ */
+#define MLD_REGION_LIST_CAPACITY 2048  /* z values of a box held in LDS (16 KiB) */
+#define MLD_REGION_HIST_BINS 512       /* bins of the histogram held in LDS, from the bin of z_min on (2 KiB) */
+enum {
+    MLD_REGION_FLAG_BAD_INPUT = 1,
+    MLD_REGION_FLAG_EMPTY_BOX = 2,
+    MLD_REGION_FLAG_HIST_FOUND = 4,
+    MLD_REGION_FLAG_HIST_CAPPED = 8,
+    MLD_REGION_FLAG_HAS_MASK = 16
+};
+
+typedef struct mld_region_depth {    /* 80 bytes, 8-byte aligned */
+    int32_t n_points;       /* counted points */
+    int32_t n_ground;       /* points the mask excluded */
+    int32_t n_seg;          /* counted points inside the histogram's bin */
+    int32_t flags;          /* MLD_REGION_FLAG_* */
+    int32_t nearest_orig;   /* original index of the nearest counted point, or -1 */
+    int32_t clip[4];        /* the clipped box x0, y0, x1, y1; -1 when empty */
+    int32_t pad_;
+    double z_min, z_max, z_median;
+    double hist_lower, hist_higher;
+} mld_region_depth;
+
+typedef struct mld_region_depths mld_region_depths;
+mld_region_depths* mld_region_depths_create(mld_ctx* ctx, int n_seq, int64_t max_boxes, const mld_params* params,
+                                            const mld_camera* camera, int* status_out);
+void mld_region_depths_destroy(mld_region_depths* rd);
+const char* mld_region_depths_last_error(const mld_region_depths* rd);
+int mld_region_depths_collect_device(mld_region_depths* rd, const int32_t* const* map, const int32_t* const* index,
+                                     const int64_t* index_len, const double* const* cam, const int64_t* n_points,
+                                     const uint32_t* const* mask_dev, const int32_t* const* boxes, const int64_t* n_boxes,
+                                     mld_region_depth* const* record_out);
+
+/*
  * Debug / parity getters (host buffers; each synchronises).
  *   mld_get_visible_count           -> _points_cs_image_visible.cols()         (DepthEstimator.cpp:192)
  *   mld_get_visible_image_points    -> getPointsCloudImageCs, 2 x Nvis col-major (:392-394)

@@ -191,6 +191,19 @@ class MldDepthImageRecord(C.Structure):
                 ("flags", C.c_int32), ("pad_", C.c_int32)]
 
 
+# mld_region_depths: the bits of mld_region_depth::flags and the two capacities of the kernel (include/mld.h)
+(MLD_REGION_FLAG_BAD_INPUT, MLD_REGION_FLAG_EMPTY_BOX, MLD_REGION_FLAG_HIST_FOUND, MLD_REGION_FLAG_HIST_CAPPED,
+ MLD_REGION_FLAG_HAS_MASK) = 1, 2, 4, 8, 16
+MLD_REGION_LIST_CAPACITY, MLD_REGION_HIST_BINS = 2048, 512
+
+
+class MldRegionDepth(C.Structure):
+    """mld_region_depth (include/mld.h): one box of mld_region_depths_collect_device, 80 bytes = 10 int64."""
+    _fields_ = [("n_points", C.c_int32), ("n_ground", C.c_int32), ("n_seg", C.c_int32), ("flags", C.c_int32),
+                ("nearest_orig", C.c_int32), ("clip", C.c_int32 * 4), ("pad_", C.c_int32), ("z_min", C.c_double),
+                ("z_max", C.c_double), ("z_median", C.c_double), ("hist_lower", C.c_double), ("hist_higher", C.c_double)]
+
+
 # Every symbol include/mld.h declares: (name, restype, argtypes)
 _P = C.POINTER
 _SIGNATURES = [
@@ -327,6 +340,11 @@ _SIGNATURES = [
     ("mld_depth_images_render_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 2 + [_P(C.c_int64), _P(C.c_void_p),
                                                  _P(C.c_int64), _P(C.c_float), _P(C.c_void_p)] + [C.c_int] * 6 +
      [_P(C.c_void_p)] * 3 + [C.c_void_p]),
+    ("mld_region_depths_create", C.c_void_p, [C.c_void_p, C.c_int, C.c_int64, _P(MldParams), _P(MldCamera), _P(C.c_int)]),
+    ("mld_region_depths_destroy", None, [C.c_void_p]),
+    ("mld_region_depths_last_error", C.c_char_p, [C.c_void_p]),
+    ("mld_region_depths_collect_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 2 + [_P(C.c_int64), _P(C.c_void_p),
+                                                   _P(C.c_int64)] + [_P(C.c_void_p)] * 2 + [_P(C.c_int64), _P(C.c_void_p)]),
     ("mld_get_visible_count", C.c_int, [C.c_void_p, C.c_int, _P(C.c_int64)]),
     ("mld_get_visible_image_points", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
     ("mld_get_point_index", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),

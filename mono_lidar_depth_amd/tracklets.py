@@ -236,7 +236,7 @@ def _result_tensor(t, shape, size, name):
 
 class _BatchObject:
     """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes, ProjectedClouds, DepthReports, PlaneInliers,
-    FeatureTraces, CoverageMaps and DepthImages share: an object of the C-ABI (mld_<_NAME>_create / _destroy /
+    FeatureTraces, CoverageMaps, DepthImages and RegionDepths share: an object of the C-ABI (mld_<_NAME>_create / _destroy /
     _last_error) on an estimator's context, its handle in the attribute named _HANDLE, the tensors of the calls that may
     still be queued, and one copy of every argument check.  The helpers, here and above:
 
@@ -990,6 +990,58 @@ class DepthImages(_BatchObject):
         self._hold(pixel_map, index, cam, record, masks, depth, depth32, type)
 
 
+class RegionDepths(_BatchObject):
+    """The foreground depth of image rectangles for S sequences per call (mld_region_depths_*, include/mld.h): per box
+    - a detector's 2-D box, a label blob's bounding box, inclusive corners, any size - the number of points, the
+    smallest, the largest and the exact median camera z, the nearest point, and the bin of the reference's
+    first-local-maximum histogram (FilterPointsMinDistBlob) with the points inside it; optionally without the points of
+    a ground plane.  It runs on the tensors ProjectedClouds.export wrote (pixel_map, index, cam) and on the masks as
+    SemanticPlanes / RansacPlanes write them.  Of the estimator's parameters the histogram's bin width and minimal count
+    are copied at creation.  Lists of S torch CUDA tensors in and out; asynchronous on the estimator's stream.  Close it
+    before its estimator."""
+
+    _NAME, _HANDLE = "region_depths", "_rd"
+    WORDS = 10  # int64 words of a record (capi.MldRegionDepth, 80 bytes)
+    DTYPE = np.dtype(capi.MldRegionDepth)
+    LIST_CAPACITY, HIST_BINS = capi.MLD_REGION_LIST_CAPACITY, capi.MLD_REGION_HIST_BINS
+
+    def __init__(self, estimator: DepthEstimator, n_seq: int, max_boxes: int, parameters=None):
+        self.S, self.max_boxes = int(n_seq), int(max_boxes)
+        self._create(estimator, self.S, self.max_boxes, *self._calibration(estimator, "parameters", "camera", parameters=parameters))
+
+    @classmethod
+    def records(cls, record) -> np.ndarray:
+        """A record tensor (int64 [n, 10]) as a NumPy record array with the fields of capi.MldRegionDepth (copies to
+        the host, which synchronises as usual)."""
+        return np.ascontiguousarray(record.cpu().numpy()).reshape(-1).view(cls.DTYPE)
+
+    def collect(self, pixel_map, index, cam, boxes, record, masks=None):
+        """pixel_map, index, cam: the S tensors each that ProjectedClouds.export wrote for the clouds (int32 [height,
+        width], int32 of a capacity that did not truncate, float64 [points, 3]; index and cam entries may be None for an
+        empty cloud); boxes: S int32 CUDA tensors (a contiguous [n, 4] each, rows (x0, y0, x1, y1), inclusive; an entry
+        None: no box); record: S int64 CUDA tensors of at least 10 * n entries (a contiguous [n, 10]:
+        capi.MldRegionDepth, see records(); None where boxes is); masks: None, or S int32 CUDA tensors (an entry None:
+        that sequence excludes nothing)."""
+        cells = self.width * self.height
+        self._lengths(pixel_map=pixel_map, index=index, cam=cam, boxes=boxes, record=record, masks=masks)
+        ns = [_entries(b, 4) for b in boxes]
+        for s in range(self.S):
+            if ns[s] > self.max_boxes:
+                raise ValueError(f"sequence {s}: {ns[s]} boxes, the object was made for {self.max_boxes}")
+            _holds(pixel_map[s], s, cells, 4, "pixel_map", required=True)
+            _holds(index[s], s, 0, 4, "index")
+            _holds(cam[s], s, 0, 8, "cam")
+            _holds(boxes[s], s, 0, 4, "boxes")
+            _holds(record[s], s, self.WORDS * ns[s], 8, "record", required=True)
+            if _at(masks, s) is not None:
+                _mask_room(masks[s], s, _entries(cam[s], 3), "masks")
+        vp = self._ptrs
+        self._check(self._lib.mld_region_depths_collect_device(
+            self._rd, vp(pixel_map), vp(index), self._i64(_entries(t) for t in index), vp(cam),
+            self._i64(_entries(t, 3) for t in cam), self._opt(masks), vp(boxes), self._i64(ns), vp(record)))
+        self._hold(pixel_map, index, cam, boxes, record, masks)
+
+
 class TrackletBatch:
     """The tracklet layer for S independent sequences at once (mld_set_clouds_planes_range_device +
     mld_tracklets_depths_device): the estimator's frame slots are two banks of S slots, sequence s keeps its current
@@ -1015,7 +1067,8 @@ class TrackletBatch:
                    "inliers": (PlaneInliers, "attach_plane_inliers", ()),
                    "feature_traces": (FeatureTraces, "attach_traces", ("max_tracks",)),
                    "coverage_maps": (CoverageMaps, "attach_coverage", ()),
-                   "depth_image_maps": (DepthImages, "attach_depth_images", ())}
+                   "depth_image_maps": (DepthImages, "attach_depth_images", ()),
+                   "region_depth_boxes": (RegionDepths, "attach_region_depths", ())}
 
     def __init__(self, parameters, camera: CameraPinhole, transform_lidar_to_cam, n_seq: int, max_tracks: int,
                  device: int = 0, list_capacity=None):
@@ -1352,6 +1405,34 @@ class TrackletBatch:
                   depth32=out["depth32"], type=out["type"])
         self.est.orderTorchAfter()
         return out
+
+    def attach_region_depths(self, max_boxes: int) -> RegionDepths:
+        """The region depths of the S sequences that region_depths() runs, for up to max_boxes boxes per sequence.  It
+        takes the estimator's parameters as they are now."""
+        return self._attach("region_depth_boxes", max_boxes)
+
+    def region_depths(self, clouds, boxes, masks=None):
+        """How far away is what lies in the rectangles `boxes` (S int32 CUDA tensors [n, 4], rows (x0, y0, x1, y1),
+        inclusive; an entry None: no box) of this frame: the projected-clouds export, then RegionDepths.collect on what
+        it wrote.  clouds: this frame's clouds (S float32 CUDA tensors: projected_clouds(cam=True, pixel_map=True) runs
+        first; attach_projected_clouds() for that), or the dict such a call returned for them with a capacity that did not
+        truncate.  masks: None, or the S int32 CUDA tensors of the ground planes as semantic_planes() / ransac_planes()
+        return them (an entry None: nothing excluded).  Returns the records, S int64 [n, 10] (capi.MldRegionDepth, see
+        RegionDepths.records(); None where boxes is).  No synchronisation: torch's current stream is made to wait for the
+        call; a host read synchronises as usual.  attach_region_depths() first."""
+        import torch
+        rd = self._attached("region_depth_boxes", "region_depths")
+        if not isinstance(clouds, dict):
+            clouds = self.projected_clouds(clouds, cam=True, pixel_map=True)
+        if clouds.get("cam") is None or clouds.get("pixel_map") is None:
+            raise ValueError("clouds: projected_clouds(cam=True, pixel_map=True) of this frame")
+        dev = clouds["pixel_map"][0].device
+        record = [torch.empty((_entries(b, 4), RegionDepths.WORDS), dtype=torch.int64, device=dev) if b is not None else None
+                  for b in boxes]
+        self.est._after_torch(*[b for b in boxes if b is not None][:1], clouds["pixel_map"][0])
+        rd.collect(clouds["pixel_map"], clouds["index"], clouds["cam"], boxes, record, masks)
+        self.est.orderTorchAfter()
+        return record
 
     def attach_labels(self) -> SemanticLabels:
         """The label assignment of the S sequences that labels() queues behind a step."""
