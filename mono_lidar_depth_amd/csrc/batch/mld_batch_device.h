@@ -1,7 +1,10 @@
 // mld_batch_device.h — the device side the batch objects have in common (mld_projected_clouds, mld_depth_reports,
-// mld_plane_inliers, mld_ransac_planes, mld_semantic_planes; mld_feature_traces takes as_global, V3 and the constants):
+// mld_plane_inliers, mld_ransac_planes, mld_semantic_planes: all of it; mld_feature_traces and the units of the coverage
+// maps, the depth images and the region depths: as_global, V3, the constants and the wavefront helpers, the first three
+// through mld_depth_path.h, which restates the per-feature depth path on top of this header):
 // __device__ functions, types and constants only - no kernel, no state, no host code, and nothing of the depth path.
 //   as_global, load_xyz, V3 / to_camera, smallest_eigvec      what the kernels of several units read and compute alike
+//   prefix_count, uniform, wave_sum, wave_max, reduce_best    ballots and butterflies over one wavefront
 //   scan_inclusive, chunk_count, scan_chunk_counts,           the pass / scan / write stream compaction: every kernel
 //   group_ranks, lane_rank                                    keeps its own name, signature, grid and epilogue
 // The host side of the compaction (the scratch arrays and their sizes) is mld_batch::CompactScratch in mld_batch_object.h.
@@ -37,6 +40,46 @@ template <int kStride, typename Index>
 __device__ __forceinline__ void load_xyz(const unsigned char* __restrict__ cloud, Index i, float& x, float& y, float& z) {
     const float4v r = *(const MLD_BATCH_GLOBAL float4u*)(cloud + (size_t)i * (size_t)kStride);
     x = r.x, y = r.y, z = r.z;
+}
+
+// ---- the wavefront: every lane must be at a call (cross-lane reads)
+// Set bits of the ballot m below this lane's.
+__device__ __forceinline__ int prefix_count(unsigned long long m) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+// A value every lane holds alike, said to the compiler: it lives in a scalar register from here on.
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// Sum and maximum by the xor butterfly: at every step a lane and its partner combine the same two values, so every lane
+// ends with the same bits.
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int d = kWave / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int d = kWave / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int d = kWave / 2; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d));
+    return v;
+}
+
+// (value descending, id ascending) over the wavefront; every lane ends with the winner.  No lane holds a NaN: a
+// candidate only ever replaces a lane's value by comparing greater.
+__device__ __forceinline__ void reduce_best(double& v, int& id) {
+#pragma unroll
+    for (int d = kWave / 2; d >= 1; d >>= 1) {
+        const double ov = __shfl_xor(v, d);
+        const int oi = __shfl_xor(id, d);
+        if (ov > v || (ov == v && oi < id)) {
+            v = ov;
+            id = oi;
+        }
+    }
 }
 
 struct V3 {

@@ -22,10 +22,11 @@
 // The only ordering between blocks is the boundary between two launches: no atomics, no flags, no fences.
 //
 // This translation unit uses the depth path through its public C-ABI only (mld_get_stream) and shares no internals with
-// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h; as_global and the size limits:
-// ../batch/mld_batch_device.h).  The far test is, operation for operation, the one of k_feature_trace
-// (../traces/mld_feature_traces.hip), Tinv is formed as mld_create forms it, and this unit is compiled without
-// contraction like the rest of the library.
+// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h; as_global, the wavefront helpers and the size
+// limits: ../batch/mld_batch_device.h).  The window rule, the far test and the mask bit are those of k_feature_trace, the
+// one copy in ../batch/mld_depth_path.h; Tinv and the half sizes are formed by that header as mld_create forms them, and the
+// refusals mld_create shares with this object are its functions.  This unit is compiled without contraction like the rest
+// of the library.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -36,6 +37,7 @@
 
 #include "../batch/mld_batch_object.h"
 #include "../batch/mld_batch_device.h"
+#include "../batch/mld_depth_path.h"
 #include "../../../include/mld.h"
 
 namespace {
@@ -96,16 +98,6 @@ struct CvCall {
     int32_t nbx, nby;             // buckets across and down
 };
 
-// NeighborFinderPixel.cpp:67-79 along one axis for the pixel p: half size and clamping in f64, (int) truncation.
-__device__ __forceinline__ void window_bounds(int p, double half, int last, int& lo, int& hi) {
-    double a = (double)p - half;
-    const double l = (a < 0.) ? 0. : a;  // std::max(a, 0.)
-    a = (double)p + half;
-    const double r = ((double)last < a) ? (double)last : a;  // std::min(a, last)
-    lo = (int)l;
-    hi = (int)r;
-}
-
 // The words and masks of the columns lo .. hi (at most 64 of them) in a bit-plane row.
 struct ColSpan {
     int w0, w1;
@@ -127,17 +119,6 @@ __device__ __forceinline__ ColSpan col_span(int lo, int hi) {
 }
 __device__ __forceinline__ int span_count(const unsigned long long* row, const ColSpan& s) {
     return (int)__popcll(row[s.w0] & s.m0) + (int)__popcll(row[s.w1] & s.m1);
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int d = kWave / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int d = kWave / 2; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d));
-    return v;
 }
 
 __device__ __forceinline__ MLD_BATCH_GLOBAL unsigned long long* plane_row(unsigned long long* planes, const CvCalib& c, int s, int p,
@@ -207,14 +188,8 @@ __global__ __launch_bounds__(kBlock) void k_coverage_classify(const CvSeq* __res
         if (q.has_plane) {
             bool far = false, inl = false;
             if (has[k]) {
-                // DepthEstimator.cpp:810 T_lidar_cam * p (fixed-size product order), :811 float, :812 float plane distance
-                const double xl = c.Tinv[3] + (c.Tinv[0] * px[k] + (c.Tinv[1] * py[k] + c.Tinv[2] * pz[k]));
-                const double yl = c.Tinv[7] + (c.Tinv[4] * px[k] + (c.Tinv[5] * py[k] + c.Tinv[6] * pz[k]));
-                const double zl = c.Tinv[11] + (c.Tinv[8] * px[k] + (c.Tinv[9] * py[k] + c.Tinv[10] * pz[k]));
-                const float xf = (float)xl, yf = (float)yl, zf = (float)zl;
-                const float d = fabsf(q.coeffs[0] * xf + q.coeffs[1] * yf + q.coeffs[2] * zf + q.coeffs[3]);
-                far = (double)d > c.roadDistThr;                     // :814-815
-                inl = (mw[k] >> ((unsigned)orig[k] & 31u)) & 1u;     // :817 CheckPointInPlane
+                far = far_from_plane(c.Tinv, q.coeffs, c.roadDistThr, {px[k], py[k], pz[k]});
+                inl = mask_bit(mw[k], orig[k]);  // (the word was loaded with the point)
             }
             mi = __ballot(inl);
             mf = __ballot(far);
@@ -466,69 +441,18 @@ __global__ __launch_bounds__(kBlock) void k_coverage_finish(const CvSeq* __restr
 
 char g_error[512] = "";  // refusals without an object: mld_coverage_maps_last_error(NULL)
 
-// 3x3 inverse by cofactors (Eigen compute_inverse<Matrix3d>): result(i,j) = cofactor<j,i> / det.
-double cof(const double m[9], int i, int j) {
-    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
-    return m[i1 * 3 + j1] * m[i2 * 3 + j2] - m[i1 * 3 + j2] * m[i2 * 3 + j1];
-}
-void inverse3(const double m[9], double out[9]) {
-    const double c0 = cof(m, 0, 0), c1 = cof(m, 1, 0), c2 = cof(m, 2, 0);
-    const double det = c0 * m[0] + (c1 * m[3] + c2 * m[6]);
-    const double invdet = 1.0 / det;
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) out[i * 3 + j] = cof(m, j, i) * invdet;
-}
-
 // Dynamic LDS of k_coverage_count: the prefix and the staged words of three bit planes.
 size_t lds_bytes(int tile_rows) { return (size_t)tile_rows * (kBlock + 3 * kStageWords) * sizeof(unsigned long long); }
-
-// Upper bound on the columns / rows a window of this half size spans: floor(2 half) + 2, and no more than the image has.
-int window_span(double half, int size) {
-    const double n = std::floor(2.0 * half) + 2.0;
-    return n > (double)size ? size : (int)n;
-}
 
 // What mld_create refuses of a parameter set, a camera and a transform that bears on the neighbour stage, with its texts;
 // and what only this object refuses.
 int refuse_config(const mld_params& P, const mld_camera& cam, const double T[12], std::string& why) {
-    if (P.neighbor_search_mode != 0) {
-        why = "neighbor_search_mode has the invalid value: " + std::to_string(P.neighbor_search_mode);  // :57
-        return MLD_ERR_UNSUPPORTED_MODE;
-    }
-    if (P.do_use_depth_segmentation) {
-        why = "DepthEstimator: Region growing not supported!";  // :608
-        return MLD_ERR_UNSUPPORTED_MODE;
-    }
-    if (P.do_use_ransac_plane) {
-        if (P.plane_estimator_use_triangle_maximation) {
-        } else if (P.plane_estimator_use_leastsquares) {
-            why = "plane_estimator_use_leastsquares (Ceres variant) is not supported";
-            return MLD_ERR_UNSUPPORTED_MODE;
-        } else if (P.plane_estimator_use_mestimator) {
-        } else {
-            why = "No road depth estimator selected.";  // :94
-            return MLD_ERR_NO_ROAD_ESTIMATOR;
-        }
-    }
-    if (P.pixelarea_search_witdh < 0 || P.pixelarea_search_height < 0) {
-        why = "negative search window";
-        return MLD_ERR_INVALID_ARG;
-    }
-    if (cam.width < 1 || cam.height < 1) {
-        why = "bad image size";
-        return MLD_ERR_INVALID_ARG;
-    }
-    if (cam.width > 65535 || cam.height > 65535 || (int64_t)cam.width * cam.height > (int64_t)1 << 30) {
-        why = "image larger than 65535 pixels on a side or 2^30 pixels in all";
-        return MLD_ERR_CAPACITY;
-    }
-    for (int t = 0; t < 12; t++)
-        if (!std::isfinite(T[t])) {
-            why = "non-finite lidar->camera transform";
-            return MLD_ERR_INVALID_ARG;
-        }
-    const double halfX2 = (double)P.pixelarea_search_witdh * 0.5 * (double)2.0f;
-    const double halfY2 = (double)P.pixelarea_search_height * 0.5 * (double)1.5f;
+    int code = refuse_modes(P, why);
+    if (code == MLD_OK) code = refuse_window_and_image(P, cam, why);  // (the intrinsics play no part in the neighbour stage)
+    if (code == MLD_OK) code = refuse_transform(T, why);
+    if (code != MLD_OK) return code;
+    double halfX1, halfY1, halfX2, halfY2;
+    window_halves(P, halfX1, halfY1, halfX2, halfY2);
     if (window_span(halfX2, cam.width) > kMaxSpan || window_span(halfY2, cam.height) > kMaxSpan) {
         why = "the wide window (2.0 x 1.5 the search area) can span more than 64 columns or more than 64 rows";
         return MLD_ERR_CAPACITY;
@@ -537,25 +461,11 @@ int refuse_config(const mld_params& P, const mld_camera& cam, const double T[12]
 }
 
 void build_calib(CvCalib& c, const mld_params& P, const mld_camera& cam, const double T[12]) {
-    // _transform_cam_to_lidar = transform_lidar_to_cam.inverse()   (DepthEstimator.cpp:44), as mld_create forms it
-    const double Lm[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
-    double Li[9];
-    inverse3(Lm, Li);
-    const double t[3] = {T[3], T[7], T[11]};
-    for (int i = 0; i < 3; i++) {
-        c.Tinv[i * 4 + 0] = Li[i * 3 + 0];
-        c.Tinv[i * 4 + 1] = Li[i * 3 + 1];
-        c.Tinv[i * 4 + 2] = Li[i * 3 + 2];
-        c.Tinv[i * 4 + 3] = (-Li[i * 3 + 0]) * t[0] + ((-Li[i * 3 + 1]) * t[1] + (-Li[i * 3 + 2]) * t[2]);
-    }
+    camera_to_lidar(T, c.Tinv);
     c.W = cam.width;
     c.H = cam.height;
     c.WW = (cam.width + 63) / 64;
-    // NeighborFinderPixel.cpp:67-68, scales (1, 1) and (2.0f, 1.5f) (DepthEstimator.cpp:509,585)
-    c.halfX1 = (double)P.pixelarea_search_witdh * 0.5 * (double)1.0f;
-    c.halfY1 = (double)P.pixelarea_search_height * 0.5 * (double)1.0f;
-    c.halfX2 = (double)P.pixelarea_search_witdh * 0.5 * (double)2.0f;
-    c.halfY2 = (double)P.pixelarea_search_height * 0.5 * (double)1.5f;
+    window_halves(P, c.halfX1, c.halfY1, c.halfX2, c.halfY2);
     c.countMin = (unsigned)P.radiusSearch_count_min;
     c.allZero = P.set_all_depths_to_zero ? 1 : 0;
     c.roadDistThr = P.ransac_plane_point_distance_treshold;

@@ -26,13 +26,16 @@
 // overflow word and a row of partial counts have one writer per launch.
 //
 // This translation unit uses the depth path through its public C-ABI only (mld_get_stream) and shares no internals with
-// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h; as_global, V3 and the size limits:
-// ../batch/mld_batch_device.h).  The device functions below are copies, operation for operation, of that path's
-// arithmetic (plane_through, viewing_ray, intersect, the histogram, the triangle search, the thresholds, the QR of the
-// M-estimator and the one-sided Jacobi on its R), Tinv and Kinv are formed as mld_create forms them, and this unit is
-// compiled without contraction like the rest of the library.  Main-path depths are bit for bit the reference's; road depths
-// agree to the project's road tolerance (the sums of the fit are taken about the list's first point, not about the camera's
-// origin: LAB.md 6.24).
+// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h; as_global, V3, the wavefront helpers and the
+// size limits: ../batch/mld_batch_device.h).  That path's arithmetic is restated, operation for operation, ONCE for the
+// batch units, in ../batch/mld_depth_path.h: the cooperative route's stages behind the window scan (hist_segment,
+// max_spanning_triangle, list_minmax_z), the tail both routes end in (finish_main with plane_through, viewing_ray,
+// intersect, the thresholds), the window rule, the far test, and the calibration with Tinv and Kinv formed as mld_create
+// forms them.  What stands here exists once - the lane route's serial walk over a lane's own list, the cell staging, the QR
+// of the M-estimator and the one-sided Jacobi on its R, the counting - but for the cooperative route's gather_window, kept
+// beside the header's for its code (see there).  This unit is compiled without contraction like the rest of the library.
+// Main-path depths are bit for bit the reference's; road depths agree to the project's road tolerance (the sums of the fit
+// are taken about the list's first point, not about the camera's origin: LAB.md 6.24).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -44,6 +47,7 @@
 
 #include "../batch/mld_batch_object.h"
 #include "../batch/mld_batch_device.h"
+#include "../batch/mld_depth_path.h"
 #include "../../../include/mld.h"
 
 namespace {
@@ -57,14 +61,11 @@ constexpr int kRowsPerWave = 4;        // grid rows a wavefront of the lane kern
 constexpr int kTileH = kWaves * kRowsPerWave;  // grid rows of a tile
 constexpr int kCap = 32;               // entries of a lane's list (narrow neighbours; road inliers): 4 B x 256 lanes each
 constexpr int kStageCells = 4096;      // cells of a tile's region that LDS holds (C0 at step 1: 84 x 31 = 2604)
-constexpr int kMaxCells = 1024;        // cells of the widest window an object accepts = entries of a cooperative list
 constexpr int kPartInts = 32;          // a row of partial counts: counts[21], n_depth, n_cooperative, bad input, 8 unused
 constexpr int kPartDepth = MLD_RESULT_TYPE_COUNT, kPartCoop = kPartDepth + 1, kPartBad = kPartDepth + 2;
-constexpr int kNone = 0x7fffffff;      // "no candidate yet" of the (value, id) reductions
 constexpr int kOrigBits = 23;          // an original index fits (kMaxPoints = 2^23 - 1); the histogram's relative bin above
 constexpr int kOrigMask = (1 << kOrigBits) - 1;
 constexpr int kRelMax = 255;           // relative bins at and beyond it are never looked at (see lane_hist)
-constexpr double kDblMax = 1.7976931348623157e308;
 constexpr int64_t kMaxGrid = 2147483647;
 
 static_assert(MLD_RESULT_TYPE_COUNT + 3 <= kPartInts, "a row of partial counts holds the record's sums");
@@ -93,16 +94,6 @@ struct DiSeq {
 };
 static_assert(sizeof(DiSeq) == 120, "120 bytes per sequence (include/mld.h, DESIGN.md)");
 
-struct DiCalib {
-    double Tinv[12];  // camera -> lidar (DepthEstimator.cpp:44)
-    double Kinv[9];   // intrinsics.inverse() (camera_pinhole.h:65)
-    double halfX1, halfY1, halfX2, halfY2;
-    double binW, thrG_min, thrG_max, thrL_val, planarThr, orthThr, roadDistThr;
-    int32_t W, H, cap;
-    uint32_t countMin;
-    int32_t minCount, useHist, thrG_en, thrG_mode, thrL_en, thrL_mode, thrL_type, useTriMax, checkPlanar, cutBehind, useRoad;
-};
-
 // What a call asks besides the descriptors.
 struct DiCall {
     mld_depth_image_record* record;  // n_seq records
@@ -110,209 +101,6 @@ struct DiCall {
     int32_t tiles_x, tiles_y;
     int32_t force_coop;  // every pixel that clears the neighbour test takes the cooperative route (the A/B library only)
 };
-
-__device__ __forceinline__ int prefix_count(unsigned long long m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// (value descending, id ascending) over the wavefront; every lane ends with the winner.  No lane holds a NaN: a
-// candidate only ever replaces a lane's value by comparing greater.
-__device__ __forceinline__ void reduce_best(double& v, int& id) {
-#pragma unroll
-    for (int d = kWave / 2; d >= 1; d >>= 1) {
-        const double ov = __shfl_xor(v, d);
-        const int oi = __shfl_xor(id, d);
-        if (ov > v || (ov == v && oi < id)) {
-            v = ov;
-            id = oi;
-        }
-    }
-}
-
-// Sum over the wavefront by the xor butterfly: at every step a lane and its partner add the same two values, so every lane
-// ends with the same bits.
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = kWave / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-// Eigen fixed-size Vector3d semantics: redux over three is func(x0, func(x1, x2))
-__device__ __forceinline__ V3 vsub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 vadd(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 vscale(V3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ V3 vdivs(V3 a, double s) { return {a.x / s, a.y / s, a.z / s}; }
-__device__ __forceinline__ double vdot(V3 a, V3 b) { return a.x * b.x + (a.y * b.y + a.z * b.z); }
-__device__ __forceinline__ double vsqnorm(V3 a) { return a.x * a.x + (a.y * a.y + a.z * a.z); }
-__device__ __forceinline__ double vnorm(V3 a) { return sqrt(vsqnorm(a)); }
-__device__ __forceinline__ V3 vnormalized(V3 a) {
-    const double z = vsqnorm(a);
-    if (z > 0.0) return vdivs(a, sqrt(z));
-    return a;
-}
-__device__ __forceinline__ V3 vcross(V3 a, V3 b) {
-    return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-
-// Cyclic Jacobi eigen-decomposition of a symmetric 3x3 (s = xx, xy, xz, yy, yz, zz): the eigenvector of the smallest
-// eigenvalue.  Only the degenerate branch of plane_through comes here.
-__device__ inline V3 smallest_eigvec3(const double s[6]) {
-    double a[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}};
-    double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 64; sweep++) {
-        const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
-        const double diag = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2];
-        if (!(off > 1e-300) || off <= 1e-32 * diag) break;
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int q = p + 1; q < 3; q++) {
-                const double apq = a[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const double akp = a[k][p], akq = a[k][q];
-                    a[k][p] = cs * akp - sn * akq;
-                    a[k][q] = sn * akp + cs * akq;
-                }
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const double apk = a[p][k], aqk = a[q][k];
-                    a[p][k] = cs * apk - sn * aqk;
-                    a[q][k] = sn * apk + cs * aqk;
-                }
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const double vkp = v[k][p], vkq = v[k][q];
-                    v[k][p] = cs * vkp - sn * vkq;
-                    v[k][q] = sn * vkp + cs * vkq;
-                }
-            }
-    }
-    // the first of the smallest diagonal entries, as a stable ascending sort picks it
-    const double d0 = a[0][0], d1 = a[1][1], d2 = a[2][2];
-    int i0 = 0;
-    double dm = d0;
-    if (d1 < dm) {
-        dm = d1;
-        i0 = 1;
-    }
-    if (d2 < dm) i0 = 2;
-    V3 n0;
-    n0.x = (i0 == 0) ? v[0][0] : ((i0 == 1) ? v[0][1] : v[0][2]);
-    n0.y = (i0 == 0) ? v[1][0] : ((i0 == 1) ? v[1][1] : v[1][2]);
-    n0.z = (i0 == 0) ? v[2][0] : ((i0 == 1) ? v[2][1] : v[2][2]);
-    return n0;
-}
-
-struct Plane {
-    V3 n;
-    double offset;
-};
-
-// Eigen::Hyperplane<double,3>::Through (call site LinePlaneIntersectionBase.cpp:41)
-__device__ __forceinline__ Plane plane_through(V3 p0, V3 p1, V3 p2) {
-    const V3 v0 = vsub(p2, p0), v1 = vsub(p1, p0);
-    const V3 n = vcross(v0, v1);
-    const double nn = vnorm(n);
-    Plane r;
-    if (nn <= vnorm(v0) * vnorm(v1) * 2.220446049250313e-16) {
-        // degenerate triangle: smallest eigenvector of m^T m, m = [v0^T; v1^T]
-        const double s[6] = {v0.x * v0.x + v1.x * v1.x, v0.x * v0.y + v1.x * v1.y, v0.x * v0.z + v1.x * v1.z,
-                             v0.y * v0.y + v1.y * v1.y, v0.y * v0.z + v1.y * v1.z, v0.z * v0.z + v1.z * v1.z};
-        r.n = smallest_eigvec3(s);
-    } else {
-        r.n = vdivs(n, nn);
-    }
-    r.offset = -vdot(p0, r.n);
-    return r;
-}
-
-// CameraPinhole::getViewingRays (camera_pinhole.h:52-69) + the flip (DepthEstimator.cpp:938-939)
-__device__ __forceinline__ V3 viewing_ray(const DiCalib& c, double u, double v) {
-    V3 d = {(c.Kinv[0] * u + c.Kinv[1] * v) + c.Kinv[2], (c.Kinv[3] * u + c.Kinv[4] * v) + c.Kinv[5],
-            (c.Kinv[6] * u + c.Kinv[7] * v) + c.Kinv[8]};
-    d = vnormalized(d);
-    if (d.z < 0) d = vscale(d, -1.0);
-    return d;
-}
-
-// LinePlaneIntersection{OrthogonalTreshold,Normal}::GetIntersection
-__device__ __forceinline__ bool intersect(const DiCalib& c, bool orth, Plane pl, V3 n0, V3 n1, double& depth) {
-    if (orth) {
-        const V3 ln = vnormalized(n1), pn = vnormalized(pl.n);
-        if (!(fabs(vdot(pn, ln)) >= c.orthThr)) return false;
-    }
-    const V3 dir = vnormalized(vsub(n1, n0));  // ParametrizedLine::Through(n0, n1)
-    const double t = -(pl.offset + vdot(pl.n, n0)) / vdot(pl.n, dir);
-    const V3 p = vadd(n0, vscale(dir, t));
-    depth = p.z;
-    return true;
-}
-
-// TresholdDepthGlobal::CheckInDepth / TresholdDepthLocal::CheckInBounds: 0 when in bounds (depth possibly adjusted) or the
-// failing result type
-__device__ __forceinline__ int apply_thresholds(const DiCalib& c, double minZ, double maxZ, double& depth) {
-    if (c.thrG_en) {
-        if (depth < c.thrG_min) {
-            if (c.thrG_mode == 0) return MLD_TresholdDepthGlobalSmallerMin;
-            depth = c.thrG_min;
-        } else if (depth > c.thrG_max) {
-            if (c.thrG_mode == 0) return MLD_TresholdDepthGlobalGreaterMax;
-            depth = c.thrG_max;
-        }
-    }
-    if (c.thrL_en) {
-        const double interval = maxZ - minZ;
-        double lo, hi;
-        if (c.thrL_type == 1) {
-            const double r = interval * c.thrL_val;
-            lo = minZ - r;
-            hi = maxZ + r;
-        } else {
-            lo = minZ - c.thrL_val;
-            hi = maxZ + c.thrL_val;
-        }
-        if (depth < lo) {
-            if (c.thrL_mode == 0) return MLD_TresholdDepthLocalSmallerMin;
-            depth = lo;
-        } else if (depth > hi) {
-            if (c.thrL_mode == 0) return MLD_TresholdDepthLocalGreaterMax;
-            depth = hi;
-        }
-    }
-    return 0;
-}
-
-// The tail of CalculateDepthSegmented (DepthEstimator.cpp:928-1036) from the three corners and the min / max z of the
-// segmented points on.
-__device__ __forceinline__ void finish_main(const DiCalib& c, double u, double v, V3 c1, V3 c2, V3 c3, double mn, double mx, int& out_type,
-                                            double& out_depth) {
-    int type = MLD_Success;
-    double depth = -1.0;
-    if (c.checkPlanar) {  // PlaneEstimationCheckPlanar.cpp:18-44
-        const V3 e1 = vnormalized(vsub(c2, c1)), e2 = vnormalized(vsub(c3, c1)), e3 = vnormalized(vsub(c3, c2));
-        const double l12 = vnorm(vcross(e1, e2)), l13 = vnorm(vcross(e1, e3)), l23 = vnorm(vcross(e2, e3));
-        if (!((l12 >= c.planarThr) && (l13 >= c.planarThr) && (l23 >= c.planarThr))) type = MLD_TriangleNotPlanar;
-    }
-    if (type == MLD_Success) {
-        const V3 dir = viewing_ray(c, u, v);
-        const V3 support = {0, 0, 0};
-        const Plane pl = plane_through(c1, c2, c3);
-        if (!intersect(c, c.orthThr > 0 /* DepthEstimator.cpp:77-81 */, pl, support, dir, depth)) type = MLD_PlaneViewrayNotOrthogonal;
-    }
-    if (type == MLD_Success) {
-        const int t = apply_thresholds(c, mn, mx, depth);
-        if (t) type = t;
-    }
-    if (type == MLD_Success && depth < 0 && c.cutBehind) type = MLD_CornerBehindCamera;
-    out_type = type;
-    out_depth = (type == MLD_Success) ? depth : -1.0;
-}
 
 // Left singular vector of the smallest singular value of M = [sqrt(w_i) (p_i - c)] from the R of the thin QR of M^T
 // (M M^T = R^T R): one-sided (Hestenes) Jacobi on the three rows of R^T, as the reference's JacobiSVD of M is restated on
@@ -360,7 +148,7 @@ __device__ inline V3 normal_from_R(const double R[6]) {
 }
 
 // The tail of RoadDepthEstimatorMEstimator::CalculateDepth (:28-74) from the weighted centre and the R of the fit on.
-__device__ __forceinline__ void finish_road(const DiCalib& c, double u, double v, V3 center, const double R[6], double mn, double mx,
+__device__ __forceinline__ void finish_road(const DepthCalib& c, double u, double v, V3 center, const double R[6], double mn, double mx,
                                             int& out_type, double& out_depth) {
     const V3 dir = viewing_ray(c, u, v);
     const V3 support = {0, 0, 0};
@@ -381,16 +169,6 @@ __device__ __forceinline__ void finish_road(const DiCalib& c, double u, double v
     out_depth = (type == MLD_SuccessRoad) ? depth : -1.0;
 }
 
-// NeighborFinderPixel.cpp:67-79 along one axis for the pixel p: half size and clamping in f64, (int) truncation.
-__device__ __forceinline__ void window_bounds(int p, double half, int last, int& lo, int& hi) {
-    double a = (double)p - half;
-    const double l = (a < 0.) ? 0. : a;  // std::max(a, 0.)
-    a = (double)p + half;
-    const double r = ((double)last < a) ? (double)last : a;  // std::min(a, last)
-    lo = (int)l;
-    hi = (int)r;
-}
-
 // A cell of the map as the path sees it: the original index of its point, -1 (empty) or -2 (a map value or an index value
 // outside the arrays: counts as empty and sets the bad-input flag of whoever meets it).
 __device__ __forceinline__ int classify_cell(const DiSeq& q, int m) {
@@ -407,7 +185,7 @@ struct Cells {
     int rx0, ry0, tw, th;
     bool staged;
 };
-__device__ __forceinline__ int cell_at(const Cells& t, const DiCalib& c, const DiSeq& q, int x, int y) {
+__device__ __forceinline__ int cell_at(const Cells& t, const DepthCalib& c, const DiSeq& q, int x, int y) {
     if (t.staged) {
         const int cx = x - t.rx0, cy = y - t.ry0;
         if ((unsigned)cx >= (unsigned)t.tw || (unsigned)cy >= (unsigned)t.th) return -1;  // (never: the region holds the windows)
@@ -422,19 +200,6 @@ __device__ __forceinline__ V3 cam_point(const DiSeq& q, int orig) {
 }
 __device__ __forceinline__ double cam_z(const DiSeq& q, int orig) { return as_global(q.cam)[3 * (size_t)orig + 2]; }
 
-// The far test and the mask bit of a wide-window neighbour (DepthEstimator.cpp:808-817).
-__device__ __forceinline__ bool far_from_plane(const DiCalib& c, const DiSeq& q, V3 p) {
-    // :810 T_lidar_cam * p (fixed-size product order), :811 float, :812 float plane distance
-    const double xl = c.Tinv[3] + (c.Tinv[0] * p.x + (c.Tinv[1] * p.y + c.Tinv[2] * p.z));
-    const double yl = c.Tinv[7] + (c.Tinv[4] * p.x + (c.Tinv[5] * p.y + c.Tinv[6] * p.z));
-    const double zl = c.Tinv[11] + (c.Tinv[8] * p.x + (c.Tinv[9] * p.y + c.Tinv[10] * p.z));
-    const float xf = (float)xl, yf = (float)yl, zf = (float)zl;
-    const float d = fabsf(q.coeffs[0] * xf + q.coeffs[1] * yf + q.coeffs[2] * zf + q.coeffs[3]);
-    return (double)d > c.roadDistThr;  // :814-815
-}
-__device__ __forceinline__ bool mask_bit(const DiSeq& q, int orig) {
-    return (as_global(q.mask)[(unsigned)orig >> 5] >> ((unsigned)orig & 31u)) & 1u;  // :817 CheckPointInPlane
-}
 // PlaneEstimationMEstimator.cpp:32: the weight of a point, 1 / absDistance to the prior
 __device__ __forceinline__ double prior_weight(const DiSeq& q, V3 p) {
     const V3 pn = {q.prior_n[0], q.prior_n[1], q.prior_n[2]};
@@ -450,7 +215,7 @@ __device__ __forceinline__ double prior_weight(const DiSeq& q, V3 p) {
 // points of the first local-maximum bin, compacted in place.  Returns their count or -1.  The bins ride in the entries'
 // upper bits, relative to the first non-empty bin and saturated at kRelMax: the scan of :70-85 starts at a non-empty bin
 // and leaves at the first empty one, so it looks at no more than k <= kCap consecutive bins.
-__device__ __forceinline__ int lane_hist(const DiCalib& c, const DiSeq& q, int* lst, int k) {
+__device__ __forceinline__ int lane_hist(const DepthCalib& c, const DiSeq& q, int* lst, int k) {
     int md = 0;  // :36-41: the largest ceil(depth) above 0
     for (int i = 0; i < k; i++) {
         double d = cam_z(q, lst[i * kBlock]);
@@ -623,7 +388,7 @@ __device__ __forceinline__ void lane_road_qr(const DiSeq& q, const int* lst, int
 }
 
 // One grid pixel on one lane.  Returns false when the pixel leaves the lane route (nothing of it is final then).
-__device__ __forceinline__ bool lane_pixel(const DiCalib& c, const DiSeq& q, const DiCall& call, const Cells& cells, int* lst, int px, int py,
+__device__ __forceinline__ bool lane_pixel(const DepthCalib& c, const DiSeq& q, const DiCall& call, const Cells& cells, int* lst, int px, int py,
                                            int& out_type, double& out_depth, bool& bad) {
     const double u = (double)px, v = (double)py;
     int xl, xh, yl, yh;
@@ -673,7 +438,7 @@ __device__ __forceinline__ bool lane_pixel(const DiCalib& c, const DiSeq& q, con
                 if (z < mn) mn = z;
                 if (z > mx) mx = z;
             }
-            finish_main(c, u, v, c1, c2, c3, mn, mx, type, depth);  // ---- B6 ----
+            type = finish_main(c, u, v, c1, c2, c3, mn, mx, nullptr, depth);  // ---- B6 ----
         }
     }
     // ---- the road fallback (:578-597) ----
@@ -689,9 +454,9 @@ __device__ __forceinline__ bool lane_pixel(const DiCalib& c, const DiSeq& q, con
                 if (o >= 0) {
                     k2++;
                     if (!anyFar) {  // (the reference leaves at the first far neighbour: the rest only counts)
-                        if (far_from_plane(c, q, cam_point(q, o))) {
+                        if (far_from_plane(c.Tinv, q.coeffs, c.roadDistThr, cam_point(q, o))) {
                             anyFar = true;
-                        } else if (mask_bit(q, o)) {
+                        } else if (mask_bit(q.mask, o)) {
                             if (kk < kCap) lst[kk * kBlock] = o;
                             kk++;
                         }
@@ -733,7 +498,7 @@ __device__ __forceinline__ void count_types(int& cnt, int lane, bool final, int 
 }
 
 // Grid: n_seq * tiles_x * tiles_y blocks.  over: kRowsPerWave words per wavefront; part: kPartInts ints per wavefront.
-__global__ __launch_bounds__(kBlock) void k_depth_image_lane(const DiSeq* __restrict__ desc, DiCalib c, DiCall call, unsigned long long* over,
+__global__ __launch_bounds__(kBlock) void k_depth_image_lane(const DiSeq* __restrict__ desc, DepthCalib c, DiCall call, unsigned long long* over,
                                                              int32_t* part) {
     __shared__ int32_t lists[kCap * kBlock];
     __shared__ int32_t staged[kStageCells];
@@ -787,18 +552,19 @@ __global__ __launch_bounds__(kBlock) void k_depth_image_lane(const DiSeq* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The cooperative route: one wavefront per pixel, lists of up to c.cap entries in LDS (dynamic; 36 bytes per entry).
+// The cooperative route: one wavefront per pixel, lists of up to c.cap entries in LDS (dynamic; 28 bytes per entry), worked
+// on by the functions of the depth path's header.
 // ---------------------------------------------------------------------------------------------------------------------
-struct Lists {
-    double* x;     // camera-frame points of the current list (the neighbours, then the segmented points in place)
-    double* y;
-    double* z;
+struct Lists : PointList {
     int32_t* aux;  // the histogram's bin of neighbour i; in the road stage its original index
 };
 
 // Window scan (NeighborFinderPixel.cpp:60-95) + 3-D gather (NeighborFinderBase.cpp:15-27): the neighbours in the
 // reference's row-major scan order; their count (wave-uniform, <= c.cap because the window has at most that many cells).
-__device__ __forceinline__ int gather_window(const DiCalib& c, const DiSeq& q, int px, int py, double halfX, double halfY, const Lists& L,
+// This unit's own copy of the depth path header's gather_window, on the staged cells' classification and integer pixels:
+// through the shared one k_depth_image_coop grew by 39 instructions and the forced cooperative route measured slower than
+// the band allows (profiles/depth_path_header.md).  A correction to either belongs in both.
+__device__ __forceinline__ int gather_window(const DepthCalib& c, const DiSeq& q, int px, int py, double halfX, double halfY, const Lists& L,
                                              int lane, bool& bad) {
     int x0, x1, y0, y1;
     window_bounds(px, halfX, c.W - 1, x0, x1);
@@ -835,151 +601,6 @@ __device__ __forceinline__ int gather_window(const DiCalib& c, const DiSeq& q, i
     if (__ballot(badl) != 0ull) bad = true;
     k = uniform(k);
     return k < c.cap ? k : c.cap;
-}
-
-// PointHistogram::FilterPointsMinDistBlob on the first k list entries: the points of the first local-maximum bin, compacted
-// in place.  Returns their count or -1.
-__device__ __forceinline__ int hist_segment(const DiCalib& c, int k, const Lists& L, int lane) {
-    int md = 0;  // :36-41: the largest ceil(depth) above 0
-    for (int i = lane; i < k; i += kWave) {
-        double d = L.z[i];
-        d = (999. < d) ? 999. : d;  // DepthEstimator.cpp:743
-        if (d > (double)md) md = (int)ceil(d);
-    }
-#pragma unroll
-    for (int s = kWave / 2; s >= 1; s >>= 1) md = max(md, __shfl_xor(md, s));
-    md = uniform(md);
-    const int binCount = (int)((double)md / c.binW + 1.0);  // :43
-    if (binCount <= 1) return -1;                           // :53
-    int bmin = kNone;
-    for (int i = lane; i < k; i += kWave) {
-        double d = L.z[i];
-        d = (999. < d) ? 999. : d;
-        const double value = (1e10 < d) ? 1e10 : d;  // Histogram.cpp:29
-        const double qd = fabs(value / c.binW);
-        const double lim = (double)binCount - 1.;
-        const int bi = (int)((lim < qd) ? lim : qd);  // Histogram.cpp:30
-        L.aux[i] = bi;
-        bmin = min(bmin, bi);
-    }
-#pragma unroll
-    for (int s = kWave / 2; s >= 1; s >>= 1) bmin = min(bmin, __shfl_xor(bmin, s));
-    bmin = uniform(bmin);
-    __syncthreads();
-    // HistogramPointDepth.cpp:70-85, started at the first non-empty bin (the empty bins ahead of it change nothing)
-    int binMaxId = -1, binMaxVal = -1, binValue = 0;
-    for (int i = bmin; i < binCount; i++) {
-        const int last = binValue;
-        int cnt = 0;
-        for (int b = 0; b < k; b += kWave) {
-            const int e = b + lane;
-            cnt += (int)__popcll(__ballot(e < k && L.aux[e] == i));
-        }
-        binValue = uniform(cnt);
-        if ((binValue > binMaxVal) && (binValue >= c.minCount)) {
-            binMaxVal = binValue;
-            binMaxId = i;
-        } else if (binValue < binMaxVal)
-            break;
-        if ((last > 0) && (binValue == 0)) return -1;
-    }
-    if (binMaxId < 0) return -1;                                      // :95
-    const double lower = (double)binMaxId * c.binW - 0.0 * c.binW;    // :99
-    const double higher = (double)binMaxId * c.binW + 1.0 * c.binW;   // :100
-    int kk = 0;
-    for (int b = 0; b < k; b += kWave) {  // :115-120
-        const int i = b + lane;
-        bool keep = false;
-        double x = 0, y = 0, z = 0;
-        if (i < k) {
-            z = L.z[i];
-            const double d = (999. < z) ? 999. : z;
-            keep = (d >= lower) && (d < higher);
-            x = L.x[i];
-            y = L.y[i];
-        }
-        const unsigned long long m = __ballot(keep);
-        const int rank = kk + prefix_count(m);  // (<= i: a lane writes at or below what this pass has read)
-        if (keep) {
-            L.x[rank] = x;
-            L.y[rank] = y;
-            L.z[rank] = z;
-        }
-        kk += (int)__popcll(m);
-    }
-    return uniform(kk);
-}
-
-__device__ __forceinline__ V3 list_point(const Lists& L, int i) { return {L.x[i], L.y[i], L.z[i]}; }
-
-// CalculatePlaneCorners on the first n list entries: the serial loops' strict '>' keeps the FIRST maximal pair in (i, j)
-// order and the first maximal k: the smallest id among the candidates at the maximum.
-__device__ __forceinline__ bool max_spanning_triangle(int n, const Lists& L, int lane, int& ci, int& cj, int& ck) {
-    if (n < 3) return false;
-    double bd = -1.0;
-    int bid = kNone;
-    for (int i = 0; i < n - 1; i++) {
-        const V3 pi = list_point(L, i);
-        for (int j = i + 1 + lane; j < n; j += kWave) {
-            const double d = vsqnorm(vsub(pi, list_point(L, j)));
-            const int id = i * n + j;
-            if (d > bd || (d == bd && id < bid)) {
-                bd = d;
-                bid = id;
-            }
-        }
-    }
-    reduce_best(bd, bid);
-    bid = uniform(bid);
-    if (bid == kNone || bd <= 0.0) return false;  // :65
-    const int bi = bid / n, bj = bid - (bid / n) * n;
-    const V3 pa = list_point(L, bi), pb = list_point(L, bj);
-    double b2 = -1.0;
-    int bk = kNone;
-    for (int kx = lane; kx < n - 1; kx += kWave) {  // :71 the last point is never considered
-        if (kx == bi || kx == bj) continue;
-        const V3 pk = list_point(L, kx);
-        const double d1 = vsqnorm(vsub(pk, pa));
-        if (d1 <= 0.0) continue;
-        const double d2 = vsqnorm(vsub(pk, pb));
-        if (d2 <= 0.0) continue;
-        const double d = d1 + d2;
-        if (d > b2) {  // (kx ascends: the first of a lane's equals stays)
-            b2 = d;
-            bk = kx;
-        }
-    }
-    reduce_best(b2, bk);
-    bk = uniform(bk);
-    if (bk == kNone) return false;
-    ci = bi;
-    cj = bj;
-    ck = bk;
-    return true;
-}
-
-// min / max of z over the first n list entries as the serial loop leaves them (TresholdDepthLocal.cpp:23-29): strict
-// comparisons from +-DBL_MAX, so a NaN never enters and the first of equal values stays.
-__device__ __forceinline__ void list_minmax_z(int n, const Lists& L, int lane, double& mn, double& mx) {
-    double a = -kDblMax, b = -kDblMax;  // the largest -z and the largest z so far
-    int ia = kNone, ib = kNone;
-    for (int i = lane; i < n; i += kWave) {
-        const double z = L.z[i];
-        if (-z > a) {
-            a = -z;
-            ia = i;
-        }
-        if (z > b) {
-            b = z;
-            ib = i;
-        }
-    }
-    reduce_best(a, ia);
-    reduce_best(b, ib);
-    ia = uniform(ia);
-    ib = uniform(ib);
-    mn = (ia == kNone) ? kDblMax : L.z[ia];
-    mx = (ib == kNone) ? -kDblMax : L.z[ib];
 }
 
 // lane_road_qr over the wavefront: the rows a_i = sqrt(w_i) (p_i - c) are written over the list (nothing reads it
@@ -1048,7 +669,7 @@ __device__ __forceinline__ void road_qr(int n, const Lists& L, int lane, const D
 }
 
 // One grid pixel on one wavefront; type and depth are wave-uniform.
-__device__ __forceinline__ void coop_pixel(const DiCalib& c, const DiSeq& q, const Lists& L, int lane, int px, int py, int& out_type,
+__device__ __forceinline__ void coop_pixel(const DepthCalib& c, const DiSeq& q, const Lists& L, int lane, int px, int py, int& out_type,
                                            double& out_depth, bool& bad) {
     const double u = (double)px, v = (double)py;
     int type = MLD_Unspecified;
@@ -1063,7 +684,8 @@ __device__ __forceinline__ void coop_pixel(const DiCalib& c, const DiSeq& q, con
     }
     // ---- B3 ----
     int ks = n_nb;
-    if (c.useHist) ks = hist_segment(c, n_nb, L, lane);
+    double lower, higher;  // (the chosen bin's borders: the trace's business)
+    if (c.useHist) ks = hist_segment(c, n_nb, L, L.aux, lane, lower, higher, [](int, int) {});
     __syncthreads();
     if (ks < 0) {
         type = MLD_HistogramNoLocalMax;
@@ -1081,7 +703,7 @@ __device__ __forceinline__ void coop_pixel(const DiCalib& c, const DiSeq& q, con
         if (ok) {
             double mn, mx;
             list_minmax_z(ks, L, lane, mn, mx);
-            finish_main(c, u, v, list_point(L, ci), list_point(L, cj), list_point(L, ck), mn, mx, type, depth);  // ---- B6 ----
+            type = finish_main(c, u, v, list_point(L, ci), list_point(L, cj), list_point(L, ck), mn, mx, nullptr, depth);  // ---- B6 ----
         }
     }
     __syncthreads();  // (the lists are rewritten from here)
@@ -1102,8 +724,8 @@ __device__ __forceinline__ void coop_pixel(const DiCalib& c, const DiSeq& q, con
                 V3 p = {0, 0, 0};
                 if (i < n_road) {
                     p = list_point(L, i);
-                    far = far_from_plane(c, q, p);
-                    inl = mask_bit(q, L.aux[i]);
+                    far = far_from_plane(c.Tinv, q.coeffs, c.roadDistThr, p);
+                    inl = mask_bit(q.mask, L.aux[i]);
                 }
                 anyFar = anyFar || (__ballot(far) != 0ull);
                 const unsigned long long m = __ballot(inl);
@@ -1132,7 +754,7 @@ __device__ __forceinline__ void coop_pixel(const DiCalib& c, const DiSeq& q, con
 }
 
 // Grid: one block of one wavefront per wavefront of the lane kernel (n_seq * tiles * kWaves).
-__global__ __launch_bounds__(kWave) void k_depth_image_coop(const DiSeq* __restrict__ desc, DiCalib c, DiCall call, const unsigned long long* over,
+__global__ __launch_bounds__(kWave) void k_depth_image_coop(const DiSeq* __restrict__ desc, DepthCalib c, DiCall call, const unsigned long long* over,
                                                             int32_t* part) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const size_t wave_id = (size_t)blockIdx.x;
@@ -1213,27 +835,6 @@ __global__ __launch_bounds__(kBlock) void k_depth_image_finish(const DiSeq* __re
 
 char g_error[512] = "";  // refusals without an object: mld_depth_images_last_error(NULL)
 
-// 3x3 inverse by cofactors (Eigen compute_inverse<Matrix3d>): result(i,j) = cofactor<j,i> / det.
-double cof(const double m[9], int i, int j) {
-    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
-    return m[i1 * 3 + j1] * m[i2 * 3 + j2] - m[i1 * 3 + j2] * m[i2 * 3 + j1];
-}
-void inverse3(const double m[9], double out[9]) {
-    const double c0 = cof(m, 0, 0), c1 = cof(m, 1, 0), c2 = cof(m, 2, 0);
-    const double det = c0 * m[0] + (c1 * m[3] + c2 * m[6]);
-    const double invdet = 1.0 / det;
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) out[i * 3 + j] = cof(m, j, i) * invdet;
-}
-
-// Upper bound on the cells a window can cover: floor(2 half) + 2 columns / rows, and no more than the image has.
-double window_cells(double halfX, double halfY, int W, int H) {
-    double nx = std::floor(2.0 * halfX) + 2.0, ny = std::floor(2.0 * halfY) + 2.0;
-    if (nx > (double)W) nx = (double)W;
-    if (ny > (double)H) ny = (double)H;
-    return nx * ny;
-}
-
 int64_t tiles_of(int grid_w, int grid_h) { return (int64_t)((grid_w + kTileW - 1) / kTileW) * (int64_t)((grid_h + kTileH - 1) / kTileH); }
 
 // What only this object refuses, then what mld_create refuses of a parameter set, a camera and a transform, with its texts.
@@ -1250,52 +851,12 @@ int refuse_config(const mld_params& P, const mld_camera& cam, const double T[12]
         why = "set_all_depths_to_zero: every depth is 0 there, the depth calls answer that without a kernel";
         return MLD_ERR_UNSUPPORTED_MODE;
     }
-    if (P.neighbor_search_mode != 0) {
-        why = "neighbor_search_mode has the invalid value: " + std::to_string(P.neighbor_search_mode);  // :57
-        return MLD_ERR_UNSUPPORTED_MODE;
-    }
-    if (P.do_use_depth_segmentation) {
-        why = "DepthEstimator: Region growing not supported!";  // :608
-        return MLD_ERR_UNSUPPORTED_MODE;
-    }
-    if (P.do_use_ransac_plane) {
-        if (P.plane_estimator_use_leastsquares) {
-            why = "plane_estimator_use_leastsquares (Ceres variant) is not supported";
-            return MLD_ERR_UNSUPPORTED_MODE;
-        } else if (P.plane_estimator_use_mestimator) {
-        } else {
-            why = "No road depth estimator selected.";  // :94
-            return MLD_ERR_NO_ROAD_ESTIMATOR;
-        }
-    }
-    if (P.pixelarea_search_witdh < 0 || P.pixelarea_search_height < 0) {
-        why = "negative search window";
-        return MLD_ERR_INVALID_ARG;
-    }
-    if (cam.width < 1 || cam.height < 1) {
-        why = "bad image size";
-        return MLD_ERR_INVALID_ARG;
-    }
-    if (cam.width > 65535 || cam.height > 65535 || (int64_t)cam.width * cam.height > (int64_t)1 << 30) {
-        why = "image larger than 65535 pixels on a side or 2^30 pixels in all";
-        return MLD_ERR_CAPACITY;
-    }
-    if (!std::isfinite(cam.focal_length) || cam.focal_length == 0.0 || !std::isfinite(cam.principal_point_x) ||
-        !std::isfinite(cam.principal_point_y)) {
-        why = "bad camera intrinsics";
-        return MLD_ERR_INVALID_ARG;
-    }
-    for (int t = 0; t < 12; t++)
-        if (!std::isfinite(T[t])) {
-            why = "non-finite lidar->camera transform";
-            return MLD_ERR_INVALID_ARG;
-        }
-    const double halfX2 = (double)P.pixelarea_search_witdh * 0.5 * (double)2.0f;
-    const double halfY2 = (double)P.pixelarea_search_height * 0.5 * (double)1.5f;
-    if (window_cells(halfX2, halfY2, cam.width, cam.height) > (double)kMaxCells) {
-        why = "the wide window (2.0 x 1.5 the search area) can cover more than 1024 cells";
-        return MLD_ERR_CAPACITY;
-    }
+    int code = refuse_modes(P, why);
+    if (code == MLD_OK) code = refuse_window_and_image(P, cam, why);
+    if (code == MLD_OK) code = refuse_intrinsics(cam, why);
+    if (code == MLD_OK) code = refuse_transform(T, why);
+    if (code == MLD_OK) code = refuse_wide_window_cells(P, cam, why);
+    if (code != MLD_OK) return code;
     if ((int64_t)n_seq * tiles_of(cam.width, cam.height) * kWaves > kMaxGrid) {
         why = "n_seq sequences of this image size need more than 2^31 - 1 blocks";
         return MLD_ERR_CAPACITY;
@@ -1303,57 +864,12 @@ int refuse_config(const mld_params& P, const mld_camera& cam, const double T[12]
     return MLD_OK;
 }
 
-void build_calib(DiCalib& c, const mld_params& P, const mld_camera& cam, const double T[12]) {
-    // _transform_cam_to_lidar = transform_lidar_to_cam.inverse()   (DepthEstimator.cpp:44), as mld_create forms it
-    const double Lm[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
-    double Li[9];
-    inverse3(Lm, Li);
-    const double t[3] = {T[3], T[7], T[11]};
-    for (int i = 0; i < 3; i++) {
-        c.Tinv[i * 4 + 0] = Li[i * 3 + 0];
-        c.Tinv[i * 4 + 1] = Li[i * 3 + 1];
-        c.Tinv[i * 4 + 2] = Li[i * 3 + 2];
-        c.Tinv[i * 4 + 3] = (-Li[i * 3 + 0]) * t[0] + ((-Li[i * 3 + 1]) * t[1] + (-Li[i * 3 + 2]) * t[2]);
-    }
-    const double K[9] = {cam.focal_length, 0, cam.principal_point_x, 0, cam.focal_length, cam.principal_point_y, 0, 0, 1};
-    inverse3(K, c.Kinv);
-    c.W = cam.width;
-    c.H = cam.height;
-    // NeighborFinderPixel.cpp:67-68, scales (1, 1) and (2.0f, 1.5f) (DepthEstimator.cpp:509,585)
-    c.halfX1 = (double)P.pixelarea_search_witdh * 0.5 * (double)1.0f;
-    c.halfY1 = (double)P.pixelarea_search_height * 0.5 * (double)1.0f;
-    c.halfX2 = (double)P.pixelarea_search_witdh * 0.5 * (double)2.0f;
-    c.halfY2 = (double)P.pixelarea_search_height * 0.5 * (double)1.5f;
-    int cap = (int)window_cells(c.halfX2, c.halfY2, cam.width, cam.height);  // (contains the narrow window's)
-    if (cap < 2) cap = 2;
-    c.cap = (cap + 1) & ~1;
-    c.binW = P.histogram_segmentation_bin_witdh;
-    c.minCount = P.histogram_segmentation_min_pointcount;
-    c.countMin = (unsigned)P.radiusSearch_count_min;
-    c.useHist = P.do_use_histogram_segmentation;
-    c.thrG_en = P.treshold_depth_enabled;
-    c.thrG_mode = P.treshold_depth_mode;
-    c.thrG_min = (double)P.treshold_depth_min;
-    c.thrG_max = (double)P.treshold_depth_max;
-    c.thrL_en = P.treshold_depth_local_enabled;
-    c.thrL_mode = P.treshold_depth_local_mode;
-    c.thrL_type = P.treshold_depth_local_valuetype;
-    c.thrL_val = P.treshold_depth_local_value;
-    c.useTriMax = P.do_use_triangle_size_maximation;
-    c.checkPlanar = P.do_check_triangleplanar_condition;
-    c.planarThr = P.triangleplanar_crossnorm_treshold;
-    c.orthThr = P.viewray_plane_orthoganality_treshold;
-    c.cutBehind = P.do_use_cut_behind_camera;
-    c.useRoad = P.do_use_ransac_plane;
-    c.roadDistThr = P.ransac_plane_point_distance_treshold;
-}
-
 }  // namespace
 
 struct mld_depth_images : mld_batch::Object {
     int n_seq = 0;
     int force_coop = 0;
-    DiCalib calib{};
+    DepthCalib calib{};
     size_t lds_bytes = 0;                  // of k_depth_image_coop
     int64_t max_tiles = 0;                 // tiles of the full grid of one sequence
     unsigned long long* d_over = nullptr;  // n_seq x max_tiles x kWaves x kRowsPerWave overflow words
@@ -1429,7 +945,7 @@ int mld_depth_images_render_device(mld_depth_images* di, const int32_t* const* m
     if (!record_out_dev) DI_REFUSE("null array record_out_dev");
     if (misaligned(record_out_dev, 7u)) DI_REFUSE("record_out_dev must be 8-byte aligned");
     if ((coeffs != nullptr) != (mask_dev != nullptr)) DI_REFUSE("coeffs and mask_dev come together or not at all");
-    const DiCalib& c = di->calib;
+    const DepthCalib& c = di->calib;
     if (step_x < 1) DI_REFUSE("step_x must be >= 1");
     if (step_y < 1) DI_REFUSE("step_y must be >= 1");
     if (grid_w < 1) DI_REFUSE("grid_w must be >= 1");

@@ -24,7 +24,7 @@
 // A box without a counted point leaves after scan 1; a box of one distinct value needs no radix pass.
 //
 // This translation unit uses the depth path through its public C-ABI only (mld_get_stream) and shares no internals with
-// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h; as_global, lane_rank and the size limits:
+// it (descriptor ring and object skeleton: ../batch/mld_batch_object.h; as_global, lane_rank, wave_sum and the size limits:
 // ../batch/mld_batch_device.h), and it is compiled without contraction like the rest of the library.
 #include <hip/hip_runtime.h>
 
@@ -177,12 +177,6 @@ __device__ __forceinline__ void for_each_z(bool listed, const unsigned long long
         for (int k = 0; k < kCells; k++)
             if (b.state[k] == 1) f(b.zb[k]);
     }
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int d = kWave / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 // Histogram.cpp:29-30 for a bin count as a double.

@@ -172,6 +172,28 @@ def dense_cloud(seed=2, holes=0.1):
     return pixel_cloud(np.stack([xs, ys], axis=1), z)
 
 
+COLLINEAR_CAM = (16, 16, 16.0, 8.0, 8.0)  # CameraPinhole(width, height, focal length, principal point)
+COLLINEAR_PIXEL = (9, 8)
+
+
+def collinear_cloud():
+    """Three points p, p + d, p + 2 d on the identity transform, every coordinate and every difference exact in f32 and f64:
+    the cross product of the triangle's edges is exactly zero, so Hyperplane::Through takes its degenerate branch (the
+    smallest eigenvector).  On the 16 x 16 camera COLLINEAR_CAM they fall into the pixels (8, 7), (9, 8) and (10, 8), all of
+    them in the narrow C0 window of COLLINEAR_PIXEL, and nothing else is in the cloud."""
+    cl = np.zeros((3, 4), dtype=np.float32)
+    cl[:, :3] = [(0.25, -0.5, 9.5), (1.0, 0.0, 10.0), (1.75, 0.5, 10.5)]
+    return cl
+
+
+def collinear_parameters():
+    """C0 with the planarity check off (it would reject the triangle before the plane), the histogram off, no road fallback;
+    triangle maximisation stays on."""
+    P = capi.params_c0().replace(do_check_triangleplanar_condition=0, do_use_histogram_segmentation=0, do_use_ransac_plane=0)
+    assert P.do_use_triangle_size_maximation == 1
+    return P
+
+
 def small_features(n, seed=0):
     """The four corners and borders of the image, positions outside it, NaN and +-inf first; then random ones, every
     other one on an integer pixel."""

@@ -1,18 +1,70 @@
-"""The device-side header the batch objects share, read as text: device functions only, nothing of the depth path."""
+"""The device-side headers the batch objects share, read as text: device functions only, nothing of the depth path."""
 import re
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
+CSRC = ROOT / "mono_lidar_depth_amd" / "csrc"
+
+
+def _holds_no_kernel_and_is_unknown_to_the_depth_path(name, public_header=False):
+    text = (CSRC / "batch" / f"{name}.h").read_text()
+    assert "__global__" not in text
+    for inc in re.findall(r'#include\s+"([^"]+)"', text):
+        path = (CSRC / "batch" / inc).resolve()
+        assert path.parent == (CSRC / "batch").resolve() or (public_header and path == (ROOT / "include" / "mld.h").resolve()), inc
+    for path in CSRC.iterdir():
+        if path.is_file() and path.name != "Makefile":
+            assert name not in path.read_text(), path.name
 
 
 def test_the_shared_device_header_holds_no_kernel_and_nothing_of_the_depth_path():
     """batch/mld_batch_device.h has no kernel, its quoted includes stay inside batch/, and no file directly in csrc/
     (the depth path, the Makefile aside) names it."""
-    csrc = ROOT / "mono_lidar_depth_amd" / "csrc"
-    text = (csrc / "batch" / "mld_batch_device.h").read_text()
-    assert "__global__" not in text
-    for inc in re.findall(r'#include\s+"([^"]+)"', text):
-        assert (csrc / "batch" / inc).resolve().parent == (csrc / "batch").resolve(), inc
-    for path in csrc.iterdir():
-        if path.is_file() and path.name != "Makefile":
-            assert "mld_batch_device" not in path.read_text(), path.name
+    _holds_no_kernel_and_is_unknown_to_the_depth_path("mld_batch_device")
+
+
+def test_the_depth_path_header_is_held_to_the_same():
+    """batch/mld_depth_path.h likewise; its quoted includes may also be the public header."""
+    _holds_no_kernel_and_is_unknown_to_the_depth_path("mld_depth_path", public_header=True)
+
+
+def test_the_depth_path_header_restates_and_does_not_reach_into_the_depth_path():
+    """batch/mld_depth_path.h includes mld_batch_device.h and the public header and nothing else of the project, names
+    neither of the depth path's internal headers, has no inline assembly, and describes its users by role: the units that
+    no file outside their directory may name are not named."""
+    text = (CSRC / "batch" / "mld_depth_path.h").read_text()
+    assert re.findall(r'#include\s+"([^"]+)"', text) == ["mld_batch_device.h", "../../../include/mld.h"]
+    assert "mld_device.h" not in text and "mld_diag.h" not in text
+    assert "asm" not in re.sub(r"//.*", "", text)
+    for unit in ("mld_coverage", "mld_depth_image", "mld_region"):
+        assert unit not in text, unit
+    assert re.search(r"^SRC\s*:=.*batch/mld_batch_device\.h batch/mld_depth_path\.h", (CSRC / "Makefile").read_text(), flags=re.M)
+
+
+def test_the_functions_of_the_depth_path_header_exist_once_among_the_batch_units():
+    """What the header took over is defined nowhere else under csrc/ outside the depth path's own files."""
+    names = ("prefix_count", "uniform", "reduce_best", "wave_sum", "wave_max", "vsub", "vadd", "vscale", "vdivs", "vdot", "vsqnorm",
+             "vnorm", "vnormalized", "vcross", "smallest_eigvec3", "plane_through", "viewing_ray", "intersect", "apply_thresholds",
+             "finish_main", "window_bounds", "far_from_plane", "mask_bit", "list_point", "max_spanning_triangle", "list_minmax_z",
+             "hist_segment", "gather_window", "inverse3", "window_cells", "window_span", "build_calib")
+    shared = {"mld_batch_device.h", "mld_depth_path.h"}
+    for path in CSRC.rglob("*"):
+        if not path.is_file() or path.parent == CSRC:
+            continue
+        code = re.sub(r"//.*", "", path.read_text())
+        for name in names:
+            defs = re.findall(r"^(?!\s*return\b)[\w \t:<>&*]*[\w>&*]\s+" + name + r"\([^;{]*\)\s*\{", code, flags=re.M)
+            if path.name in shared:
+                continue
+            # (the coverage maps fill their own calibration: same name, their own struct)
+            if name == "build_calib" and path.name == "mld_coverage_maps.hip":
+                continue
+            # (the cooperative route of the depth images keeps its gather: profiles/depth_path_header.md)
+            if name == "gather_window" and path.name == "mld_depth_images.hip":
+                assert len(defs) == 1 and "profiles/depth_path_header.md" in path.read_text()
+                continue
+            assert defs == [], (path.name, name)
+    both = "".join(re.sub(r"//.*", "", (CSRC / "batch" / h).read_text()) for h in shared)
+    for name in names:
+        n = len(re.findall(r"^(?:template[^\n]*\n)?[\w \t:<>&*]*[\w>&*]\s+" + name + r"\([^;{]*\)\s*\{", both, flags=re.M))
+        assert n == (2 if name in ("wave_sum", "mask_bit") else 1), (name, n)

@@ -177,9 +177,9 @@ def test_the_coverage_maps_are_a_translation_unit_of_their_own():
     csrc = ROOT / "mono_lidar_depth_amd" / "csrc"
     text = (csrc / "coverage" / "mld_coverage_maps.hip").read_text()
     assert re.findall(r'#include\s+"([^"]+)"', text) == ["../batch/mld_batch_object.h", "../batch/mld_batch_device.h",
-                                                           "../../../include/mld.h"]
+                                                           "../batch/mld_depth_path.h", "../../../include/mld.h"]
     assert "mld_device.h" not in text and "mld_diag.h" not in text
-    code = re.sub(r"//.*", "", text)
+    code = re.sub(r"//.*", "", text + (csrc / "batch" / "mld_depth_path.h").read_text())  # (the unit and the header its code moved to)
     assert "asm" not in code and "atomic" not in code.lower() and "__threadfence" not in code
     assert re.findall(r"__global__[^\n]*\bvoid (\w+)\(", text) == ["k_coverage_classify", "k_coverage_count", "k_coverage_finish"]
     assert len(re.findall(r"hipLaunchKernelGGL\(", text)) == 3  # (+ the descriptor upload: four launches)

@@ -359,6 +359,43 @@ def test_through_the_product_against_the_depth_call(kitti_frames):
         tb.est.close()
 
 
+@pytest.mark.parametrize("route", ["shipped", "ab-coop"])
+def test_three_collinear_neighbours_take_the_degenerate_plane_like_the_depth_call(monkeypatch, route):
+    """16 x 16, one sequence, one grid pixel whose narrow window holds exactly three points on a line: Hyperplane::Through
+    takes its smallest-eigenvector branch, on the lane route and (A/B library) on the cooperative one.  Type and depth equal
+    mld_calculate_depths_device on the same cloud, bit for bit."""
+    import torch
+    import feature_trace_restatement as R
+    from mono_lidar_depth_amd import CameraPinhole
+    if route != "shipped":
+        monkeypatch.setattr(capi, "_lib", capi.load_ab())
+        monkeypatch.setenv("MLD_DEPTH_IMAGE_COOP", "1")
+    P, cl = R.collinear_parameters(), R.collinear_cloud()
+    fr = F.Frame(P, CameraPinhole(*R.COLLINEAR_CAM), F.SMALL_T, cl, None)
+    px, py = R.COLLINEAR_PIXEL
+    assert int((fr.pm[py - 4:py + 5, px - 3:px + 4] >= 0).sum()) == 3 == int((fr.pm >= 0).sum())
+    est = make_estimator(P, camera=fr.cam_model, T=fr.T, max_frames=1)
+    try:
+        di = DepthImages(est, 1)
+        got = run(di, prepare([fr], grid=(px, py, 1, 1, 1, 1), planes=False))[0]
+        assert got["rec"]["n_pixels"] == 1 and got["rec"]["n_cooperative"] == (1 if route == "ab-coop" else 0)
+        dev = torch.device("cuda:0")
+        est.setInputCloud(cl)
+        depth = torch.empty(1, dtype=torch.float64, device=dev)
+        types = torch.empty(1, dtype=torch.int32, device=dev)
+        est.CalculateDepths([torch.from_numpy(np.array([[px, py]], dtype=np.float64)).to(dev)], [depth], [types])
+        est.synchronize()
+        depth, types = depth.cpu().numpy(), types.cpu().numpy()
+        print(f"collinear {route}: depth call type {types[0]} depth {depth[0]!r}; image type {got['type'][0, 0]} "
+              f"depth {got['depth'][0, 0]!r}")
+        assert int(got["type"][0, 0]) == int(types[0])
+        assert np.array_equal(got["depth"].reshape(-1).view(np.int64), depth.view(np.int64))
+        assert np.array_equal(got["depth32"].reshape(-1).view(np.uint32), depth.astype(np.float32).view(np.uint32))
+        di.close()
+    finally:
+        est.close()
+
+
 def test_bad_map_and_index_values_count_as_empty_cells(estimators):
     """Map values >= index_len and < -1, and index values >= n_points or negative, that still point INSIDE the allocations:
     a missing check shows as a wrong result, not as a fault.  Expected: the frame without those cells, and the flag."""

@@ -187,9 +187,9 @@ def test_the_traces_are_a_translation_unit_of_their_own():
     csrc = ROOT / "mono_lidar_depth_amd" / "csrc"
     text = (csrc / "traces" / "mld_feature_traces.hip").read_text()
     assert re.findall(r'#include\s+"([^"]+)"', text) == ["../batch/mld_batch_object.h", "../batch/mld_batch_device.h",
-                                                           "../../../include/mld.h"]
+                                                           "../batch/mld_depth_path.h", "../../../include/mld.h"]
     assert "mld_device.h" not in text and "mld_diag.h" not in text
-    assert "asm" not in re.sub(r"//.*", "", text)
+    assert "asm" not in re.sub(r"//.*", "", text + (csrc / "batch" / "mld_depth_path.h").read_text())
     assert re.findall(r"__global__[^\n]*\bvoid (\w+)\(", text) == ["k_feature_trace"]
     mk = (csrc / "Makefile").read_text()
     link_lines = [ln for ln in mk.splitlines() if "-shared" in ln]

@@ -482,6 +482,40 @@ def test_hdl64_frame_against_the_restatement_and_the_product(hdl64):
         est.close()
 
 
+def test_three_collinear_neighbours_take_the_degenerate_plane_like_the_depth_call():
+    """16 x 16, one sequence, one feature whose narrow window holds exactly three points on a line: Hyperplane::Through
+    takes its smallest-eigenvector branch.  main_type and main_depth equal mld_calculate_depths_device on the same cloud,
+    bit for bit."""
+    import torch
+    P, cl = R.collinear_parameters(), R.collinear_cloud()
+    cam = CameraPinhole(*R.COLLINEAR_CAM)
+    uv = np.array([R.COLLINEAR_PIXEL], dtype=np.float64)
+    fr = R.Restatement(P, cl, None, cam, SMALL_T)
+    est = make_estimator(P, camera=cam, T=SMALL_T, max_frames=1)
+    try:
+        ft = FeatureTraces(est, 1, 1)
+        got = run(ft, prepare([fr], [uv], 8, planes=False))[0]
+        assert got["guards"]
+        g = got["rec"][0]
+        assert (g["n_nb"], g["n_seg"], g["road_state"]) == (3, 3, R.NOT_REACHED) and g["corner_pos"].tolist() == [0, 2, 1]
+        c = g["corners"].reshape(3, 3)
+        assert np.array_equal(np.cross(c[2] - c[0], c[1] - c[0]), np.zeros(3))  # (the triangle is degenerate exactly)
+        dev = torch.device("cuda:0")
+        est.setInputCloud(cl)
+        depth = torch.empty(1, dtype=torch.float64, device=dev)
+        types = torch.empty(1, dtype=torch.int32, device=dev)
+        est.CalculateDepths([torch.from_numpy(uv).to(dev)], [depth], [types])
+        est.synchronize()
+        depth, types = depth.cpu().numpy(), types.cpu().numpy()
+        print(f"collinear: depth call type {types[0]} depth {depth[0]!r}; trace type {g['main_type']} depth {g['main_depth']!r} "
+              f"plane {g['plane_n'].tolist()} {g['plane_offset']!r}")
+        assert g["main_type"] == types[0]
+        assert np.array_equal(np.array([g["main_depth"]]).view(np.int64), depth.view(np.int64))
+        ft.close()
+    finally:
+        est.close()
+
+
 def test_tracklet_batch_traces_runs_on_the_exported_clouds(hdl64):
     """TrackletBatch.traces on the products of projected_clouds(cam=True, pixel_map=True) and the planes of the frame
     table: the records of the integer-pixel features equal the restatement."""
