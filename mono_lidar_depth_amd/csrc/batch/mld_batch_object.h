@@ -3,11 +3,16 @@
 // each a translation unit of its own that includes this header, include/mld.h and - for what their kernels share -
 // mld_batch_device.h only):
 //   Object         the fields every object has (context, stream, device, last error), fail() and the MLD_HIP check on them
+//   DeviceBuffer<T>  one allocation of device (or pinned host) memory, returned by its destructor: the only place of
+//                  the batch objects that takes or returns GPU memory
 //   DescRing<D>    the per-call table of n_seq descriptors: staged on the host, copied into one of kGens pinned
 //                  generations and moved to device memory by a kernel on the object's stream
 //   CompactScratch the device scratch of a pass / scan / write stream compaction (mld_batch_device.h) and its sizes
 //   create_object / release_object / destroy_object   the skeleton of mld_*_create and mld_*_destroy
 //   no_object, misaligned, with_stride   the refusal of a call on no object, the alignment test, the 16 / 32 dispatch
+// Who frees what: an object's members own its memory (buffers, ring, scratch), so `delete` returns all of it and a unit
+// has nothing to free by hand.  release_object deletes after the stream has been synchronised, with the object's
+// device current; objects live on the heap only (create_object / release_object), so no destructor runs at exit.
 // The objects share these TYPES; every object has its own ring, and none of this is shared with the context's own
 // upload ring in mld_api.hip.
 #pragma once
@@ -76,22 +81,56 @@ void with_stride(int stride_bytes, F f) {
         }                                                                                                  \
     } while (0)
 
+// One allocation of `count` T that is returned when its owner goes: device memory, or (Pinned) page-locked host memory.
+// Move-only, starts null, never grows.
+template <typename T, bool Pinned = false>
+class DeviceBuffer {
+    T* p_ = nullptr;
+
+public:
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer&& b) noexcept : p_(b.p_) { b.p_ = nullptr; }
+    DeviceBuffer& operator=(DeviceBuffer&&) = delete;
+    ~DeviceBuffer() {
+        if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+    }
+
+    int allocate(Object* o, size_t count) {
+        if (Pinned)
+            MLD_HIP(o, hipHostMalloc((void**)&p_, count * sizeof(T), hipHostMallocDefault));
+        else
+            MLD_HIP(o, hipMalloc((void**)&p_, count * sizeof(T)));
+        return MLD_OK;
+    }
+
+    T* get() const { return p_; }
+};
+
 template <typename Desc>
 struct DescRing {
     static_assert(sizeof(Desc) % 4 == 0, "the upload kernel moves 32-bit words");
-    Desc* d_desc = nullptr;            // what the kernels of a call read
-    unsigned char* up_base = nullptr;  // pinned: kGens generations of n_seq descriptors
+    DeviceBuffer<Desc> d_desc;                  // what the kernels of a call read
+    DeviceBuffer<unsigned char, true> up_base;  // pinned: kGens generations of n_seq descriptors
     size_t gen_bytes = 0;
-    hipEvent_t up_ev[kGens] = {};      // recorded behind the upload kernel that reads the generation
+    hipEvent_t up_ev[kGens] = {};               // recorded behind the upload kernel that reads the generation
     bool up_busy[kGens] = {};
     int up_next = 0;
-    std::vector<Desc> stage;           // the next call's descriptors, filled by the caller
+    std::vector<Desc> stage;                    // the next call's descriptors, filled by the caller
+
+    DescRing() = default;
+    DescRing(const DescRing&) = delete;
+    // After the stream has been synchronised (release_object): the events first, then the two buffers.
+    ~DescRing() {
+        for (int g = 0; g < kGens; g++)
+            if (up_ev[g]) (void)hipEventDestroy(up_ev[g]);
+    }
 
     int allocate(Object* o, int n_seq) {
         stage.assign((size_t)n_seq, Desc{});
         gen_bytes = (size_t)n_seq * sizeof(Desc);
-        MLD_HIP(o, hipMalloc((void**)&d_desc, gen_bytes));
-        MLD_HIP(o, hipHostMalloc((void**)&up_base, gen_bytes * kGens, hipHostMallocDefault));
+        int rc;
+        if ((rc = d_desc.allocate(o, (size_t)n_seq))) return rc;
+        if ((rc = up_base.allocate(o, gen_bytes * kGens))) return rc;
         for (int g = 0; g < kGens; g++) MLD_HIP(o, hipEventCreateWithFlags(&up_ev[g], hipEventDisableTiming));
         return MLD_OK;
     }
@@ -100,79 +139,67 @@ struct DescRing {
     int upload(Object* o) {
         const int g = up_next;
         if (up_busy[g]) MLD_HIP(o, hipEventSynchronize(up_ev[g]));  // (only when kGens uploads are still queued)
-        unsigned char* pinned = up_base + (size_t)g * gen_bytes;
+        unsigned char* pinned = up_base.get() + (size_t)g * gen_bytes;
         std::memcpy(pinned, stage.data(), gen_bytes);
         const int words = (int)(gen_bytes / 4);
         hipLaunchKernelGGL(k_batch_upload, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, o->stream,
-                           reinterpret_cast<uint32_t*>(d_desc), reinterpret_cast<const uint32_t*>(pinned), words);
+                           reinterpret_cast<uint32_t*>(d_desc.get()), reinterpret_cast<const uint32_t*>(pinned), words);
         MLD_HIP(o, hipGetLastError());
         MLD_HIP(o, hipEventRecord(up_ev[g], o->stream));
         up_busy[g] = true;
         up_next = (g + 1) % kGens;
         return MLD_OK;
     }
-
-    // After the stream has been synchronised (release_object).
-    void release() {
-        if (d_desc) (void)hipFree(d_desc);
-        if (up_base) (void)hipHostFree(up_base);
-        for (int g = 0; g < kGens; g++)
-            if (up_ev[g]) (void)hipEventDestroy(up_ev[g]);
-    }
 };
 
 // The device scratch of a stream compaction over sequences of up to max_items items: one 64-bit mask per group of 64
 // items, and per chunk of `chunk` items (+ 1: the total) `columns` counts side by side.
 struct CompactScratch {
-    unsigned long long* d_gm = nullptr;
-    int* d_cpre = nullptr;
+    DeviceBuffer<unsigned long long> d_gm;
+    DeviceBuffer<int> d_cpre;
     long long groups_per_seq = 0;
     long long chunks_per_seq = 0;
 
     int allocate(Object* o, int n_seq, int64_t max_items, int chunk, int columns, bool masks = true) {
         groups_per_seq = (long long)((max_items + 63) / 64);
         chunks_per_seq = (long long)((max_items + chunk - 1) / chunk);
-        if (masks) MLD_HIP(o, hipMalloc((void**)&d_gm, (size_t)n_seq * (size_t)groups_per_seq * sizeof(unsigned long long)));
-        MLD_HIP(o, hipMalloc((void**)&d_cpre, (size_t)n_seq * (size_t)(chunks_per_seq + 1) * (size_t)columns * sizeof(int)));
-        return MLD_OK;
-    }
-
-    // After the stream has been synchronised (release_object).
-    void release() {
-        if (d_gm) (void)hipFree(d_gm);
-        if (d_cpre) (void)hipFree(d_cpre);
+        int rc;
+        if (masks && (rc = d_gm.allocate(o, (size_t)n_seq * (size_t)groups_per_seq))) return rc;
+        return d_cpre.allocate(o, (size_t)n_seq * (size_t)(chunks_per_seq + 1) * (size_t)columns);
     }
 };
 
-// Obj: an Object with a member `ring`.  free_own(obj) frees the device memory the object allocated besides its ring.
-template <typename Obj, typename FreeOwn>
-void release_object(Obj* o, FreeOwn free_own) {
+// Obj: an Object whose members own what it allocated (DeviceBuffer, DescRing, CompactScratch): delete returns all of it,
+// with the object's device current and nothing of the object in flight.
+template <typename Obj>
+void release_object(Obj* o) {
     if (o->stream) (void)hipStreamSynchronize(o->stream);
-    free_own(o);
-    o->ring.release();
     delete o;
 }
 
-template <typename Obj, typename FreeOwn>
-void destroy_object(Obj* o, FreeOwn free_own) {
+template <typename Obj>
+void destroy_object(Obj* o) {
     if (!o) return;
     (void)hipSetDevice(o->device);
-    release_object(o, free_own);
+    release_object(o);
 }
 
-// mld_*_create behind the argument checks: `refusal` is the caller's verdict on its arguments (sizes first, then the
-// context, then the rest; null: none), `no_object_error` its string for mld_*_last_error(NULL).  init(obj) fills in the
-// object's own fields and allocates, the ring included, on the stream's device.
-template <typename Obj, typename Init, typename FreeOwn>
+// mld_*_create behind the argument checks, which hand in at most one verdict on the arguments, in the caller's own order
+// (the sizes first, then the context, then the rest; or the context last): `refusal`, a whole text refused with
+// MLD_ERR_INVALID_ARG (null: none), or `code` and `why`, refused with that code as "<fn>: <why>" (MLD_OK: none).
+// `no_object_error` is the caller's string for mld_*_last_error(NULL).  init(obj) fills in the object's own fields and
+// allocates, the ring included, on the stream's device.  Objects live on the heap only.
+template <typename Obj, typename Init>
 Obj* create_object(char (&no_object_error)[512], const char* fn, const char* refusal, mld_ctx* ctx, int* status_out, Init init,
-                   FreeOwn free_own) {
-    auto refuse = [&](int code, const char* prefix, const char* text) -> Obj* {
+                   int code = MLD_OK, const char* why = "") {
+    auto refuse = [&](int status, const char* prefix, const char* text) -> Obj* {
         std::snprintf(no_object_error, sizeof(no_object_error), "%s%s", prefix, text);
-        if (status_out) *status_out = code;
+        if (status_out) *status_out = status;
         return nullptr;
     };
     if (status_out) *status_out = MLD_OK;
     if (refusal) return refuse(MLD_ERR_INVALID_ARG, "", refusal);
+    if (code != MLD_OK) return refuse(code, fn, (std::string(": ") + why).c_str());
     Obj* o = new (std::nothrow) Obj();
     if (!o) return refuse(MLD_ERR_HIP, fn, ": out of host memory");
     o->ctx = ctx;
@@ -188,7 +215,7 @@ Obj* create_object(char (&no_object_error)[512], const char* fn, const char* ref
     if (rc != MLD_OK) {
         const std::string text = std::string(": ") + o->err;
         o->stream = nullptr;  // (nothing of the object is in flight that the frees would not wait for)
-        release_object(o, free_own);
+        release_object(o);
         return refuse(rc, fn, text.c_str());
     }
     return o;

@@ -218,8 +218,6 @@ int allocate(mld_projected_clouds* pc) {
     return pc->scratch.allocate(pc, pc->n_seq, pc->max_points, kChunk, 1);
 }
 
-void free_own(mld_projected_clouds* pc) { pc->scratch.release(); }
-
 template <int kStride>
 void launch_all(mld_projected_clouds* pc, int chunks, bool any_map, int64_t* n_visible) {
     const unsigned S = (unsigned)pc->n_seq;
@@ -229,16 +227,16 @@ void launch_all(mld_projected_clouds* pc, int chunks, bool any_map, int64_t* n_v
         const long long per_block = (long long)kBlock * kFillPerThread;
         const long long blocks = (cells + per_block - 1) / per_block;
         hipLaunchKernelGGL(k_pc_fill, dim3(S, blocks < (long long)kFillMaxBlocks ? (unsigned)blocks : kFillMaxBlocks), dim3(kBlock),
-                           0, pc->stream, pc->ring.d_desc, cells);
+                           0, pc->stream, pc->ring.d_desc.get(), cells);
     }
     if (chunks > 0)
-        hipLaunchKernelGGL(k_pc_pass<kStride>, dim3(S, (unsigned)chunks), dim3(kBlock), 0, pc->stream, pc->ring.d_desc, pc->calib,
-                           cs.d_gm, cs.groups_per_seq, cs.d_cpre, cs.chunks_per_seq);
-    hipLaunchKernelGGL(k_pc_scan, dim3(S), dim3(256), 0, pc->stream, pc->ring.d_desc, cs.d_cpre, cs.chunks_per_seq,
+        hipLaunchKernelGGL(k_pc_pass<kStride>, dim3(S, (unsigned)chunks), dim3(kBlock), 0, pc->stream, pc->ring.d_desc.get(), pc->calib,
+                           cs.d_gm.get(), cs.groups_per_seq, cs.d_cpre.get(), cs.chunks_per_seq);
+    hipLaunchKernelGGL(k_pc_scan, dim3(S), dim3(256), 0, pc->stream, pc->ring.d_desc.get(), cs.d_cpre.get(), cs.chunks_per_seq,
                        reinterpret_cast<long long*>(n_visible));
     if (chunks > 0)
-        hipLaunchKernelGGL(k_pc_write<kStride>, dim3(S, (unsigned)chunks), dim3(kBlock), 0, pc->stream, pc->ring.d_desc, pc->calib,
-                           cs.d_gm, cs.groups_per_seq, cs.d_cpre, cs.chunks_per_seq);
+        hipLaunchKernelGGL(k_pc_write<kStride>, dim3(S, (unsigned)chunks), dim3(kBlock), 0, pc->stream, pc->ring.d_desc.get(), pc->calib,
+                           cs.d_gm.get(), cs.groups_per_seq, cs.d_cpre.get(), cs.chunks_per_seq);
 }
 
 }  // namespace
@@ -270,11 +268,10 @@ mld_projected_clouds* mld_projected_clouds_create(mld_ctx* ctx, int n_seq, int64
         pc->calib.H = camera->height;
         return allocate(pc);
     };
-    return mld_batch::create_object<mld_projected_clouds>(g_error, "mld_projected_clouds_create", refusal(), ctx, status_out, init,
-                                                          free_own);
+    return mld_batch::create_object<mld_projected_clouds>(g_error, "mld_projected_clouds_create", refusal(), ctx, status_out, init);
 }
 
-void mld_projected_clouds_destroy(mld_projected_clouds* pc) { mld_batch::destroy_object(pc, free_own); }
+void mld_projected_clouds_destroy(mld_projected_clouds* pc) { mld_batch::destroy_object(pc); }
 
 const char* mld_projected_clouds_last_error(const mld_projected_clouds* pc) { return pc ? pc->err.c_str() : g_error; }
 

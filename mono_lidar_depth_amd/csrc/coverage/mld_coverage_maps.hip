@@ -484,23 +484,12 @@ struct mld_coverage_maps : mld_batch::Object {
     int use_road = 0;
     CvCalib calib{};
     size_t lds_bytes = 0;
-    unsigned long long* d_planes = nullptr;  // n_seq x 3 x H x WW words
-    int32_t* d_partA = nullptr;              // n_seq x blocksA x 4
-    int32_t* d_partB = nullptr;              // n_seq x strips x bands x 4
-    uint16_t* d_nbfull = nullptr;            // n_seq x W x H: the bucket partials
+    mld_batch::DeviceBuffer<unsigned long long> d_planes;  // n_seq x 3 x H x WW words
+    mld_batch::DeviceBuffer<int32_t> d_partA;              // n_seq x blocksA x 4
+    mld_batch::DeviceBuffer<int32_t> d_partB;              // n_seq x strips x bands x 4
+    mld_batch::DeviceBuffer<uint16_t> d_nbfull;            // n_seq x W x H: the bucket partials
     mld_batch::DescRing<CvSeq> ring;
 };
-
-namespace {
-
-void free_own(mld_coverage_maps* cm) {
-    if (cm->d_planes) (void)hipFree(cm->d_planes);
-    if (cm->d_partA) (void)hipFree(cm->d_partA);
-    if (cm->d_partB) (void)hipFree(cm->d_partB);
-    if (cm->d_nbfull) (void)hipFree(cm->d_nbfull);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -516,9 +505,10 @@ mld_coverage_maps* mld_coverage_maps_create(mld_ctx* ctx, int n_seq, const mld_p
         return nullptr;
     };
     const char* bad = refusal();
+    std::string why;
+    int code = MLD_OK;
     if (!bad) {  // (what is refused with a status of its own; still nothing of the context is used)
-        std::string why;
-        int code = refuse_config(*params, *camera, T_cam_lidar, why);
+        code = refuse_config(*params, *camera, T_cam_lidar, why);
         if (code == MLD_OK) {
             CvCalib c{};
             build_calib(c, *params, *camera, T_cam_lidar);
@@ -527,11 +517,6 @@ mld_coverage_maps* mld_coverage_maps_create(mld_ctx* ctx, int n_seq, const mld_p
                 why = "n_seq sequences of this image size need more than 2^31 - 1 blocks";
                 code = MLD_ERR_CAPACITY;
             }
-        }
-        if (code != MLD_OK) {
-            std::snprintf(g_error, sizeof(g_error), "mld_coverage_maps_create: %s", why.c_str());
-            if (status_out) *status_out = code;
-            return nullptr;
         }
     }
     auto init = [&](mld_coverage_maps* cm) -> int {
@@ -545,16 +530,18 @@ mld_coverage_maps* mld_coverage_maps_create(mld_ctx* ctx, int n_seq, const mld_p
         MLD_HIP(cm, hipFuncSetAttribute(reinterpret_cast<const void*>(k_coverage_count), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)lds_bytes(kMaxBand / 2 + kMaxSpan)));
         const size_t S = (size_t)n_seq;
-        MLD_HIP(cm, hipMalloc((void**)&cm->d_planes, S * 3 * (size_t)c.H * (size_t)c.WW * sizeof(unsigned long long)));
-        MLD_HIP(cm, hipMalloc((void**)&cm->d_partA, S * (size_t)c.blocksA * 4 * sizeof(int32_t)));
-        MLD_HIP(cm, hipMalloc((void**)&cm->d_partB, S * (size_t)c.strips * (size_t)c.bands * 4 * sizeof(int32_t)));
-        MLD_HIP(cm, hipMalloc((void**)&cm->d_nbfull, S * (size_t)c.W * (size_t)c.H * sizeof(uint16_t)));
+        int rc;
+        if ((rc = cm->d_planes.allocate(cm, S * 3 * (size_t)c.H * (size_t)c.WW))) return rc;
+        if ((rc = cm->d_partA.allocate(cm, S * (size_t)c.blocksA * 4))) return rc;
+        if ((rc = cm->d_partB.allocate(cm, S * (size_t)c.strips * (size_t)c.bands * 4))) return rc;
+        if ((rc = cm->d_nbfull.allocate(cm, S * (size_t)c.W * (size_t)c.H))) return rc;
         return cm->ring.allocate(cm, n_seq);
     };
-    return mld_batch::create_object<mld_coverage_maps>(g_error, "mld_coverage_maps_create", bad, ctx, status_out, init, free_own);
+    return mld_batch::create_object<mld_coverage_maps>(g_error, "mld_coverage_maps_create", bad, ctx, status_out, init, code,
+                                                       why.c_str());
 }
 
-void mld_coverage_maps_destroy(mld_coverage_maps* cm) { mld_batch::destroy_object(cm, free_own); }
+void mld_coverage_maps_destroy(mld_coverage_maps* cm) { mld_batch::destroy_object(cm); }
 
 const char* mld_coverage_maps_last_error(const mld_coverage_maps* cm) { return cm ? cm->err.c_str() : g_error; }
 
@@ -632,14 +619,14 @@ int mld_coverage_maps_collect_device(mld_coverage_maps* cm, const int32_t* const
     MLD_HIP(cm, hipSetDevice(cm->device));
     const int rc = cm->ring.upload(cm);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_coverage_classify, dim3((unsigned)((int64_t)S * c.blocksA)), dim3(kBlock), 0, cm->stream, cm->ring.d_desc, c,
-                       cm->d_planes, cm->d_partA);
+    hipLaunchKernelGGL(k_coverage_classify, dim3((unsigned)((int64_t)S * c.blocksA)), dim3(kBlock), 0, cm->stream, cm->ring.d_desc.get(), c,
+                       cm->d_planes.get(), cm->d_partA.get());
     MLD_HIP(cm, hipGetLastError());
     hipLaunchKernelGGL(k_coverage_count, dim3((unsigned)((int64_t)S * c.strips * c.bands)), dim3(kBlock), cm->lds_bytes, cm->stream,
-                       cm->ring.d_desc, c, call, cm->d_planes, cm->d_partB, cm->d_nbfull);
+                       cm->ring.d_desc.get(), c, call, cm->d_planes.get(), cm->d_partB.get(), cm->d_nbfull.get());
     MLD_HIP(cm, hipGetLastError());
-    hipLaunchKernelGGL(k_coverage_finish, dim3((unsigned)((int64_t)S * per_seq)), dim3(kBlock), 0, cm->stream, cm->ring.d_desc, c, call,
-                       cm->d_partA, cm->d_partB, cm->d_nbfull, (int)per_seq);
+    hipLaunchKernelGGL(k_coverage_finish, dim3((unsigned)((int64_t)S * per_seq)), dim3(kBlock), 0, cm->stream, cm->ring.d_desc.get(), c, call,
+                       cm->d_partA.get(), cm->d_partB.get(), cm->d_nbfull.get(), (int)per_seq);
     MLD_HIP(cm, hipGetLastError());
     return MLD_OK;
 }

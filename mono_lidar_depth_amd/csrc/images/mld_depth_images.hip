@@ -872,19 +872,10 @@ struct mld_depth_images : mld_batch::Object {
     DepthCalib calib{};
     size_t lds_bytes = 0;                  // of k_depth_image_coop
     int64_t max_tiles = 0;                 // tiles of the full grid of one sequence
-    unsigned long long* d_over = nullptr;  // n_seq x max_tiles x kWaves x kRowsPerWave overflow words
-    int32_t* d_part = nullptr;             // n_seq x max_tiles x kWaves x kPartInts partial counts
+    mld_batch::DeviceBuffer<unsigned long long> d_over;  // n_seq x max_tiles x kWaves x kRowsPerWave overflow words
+    mld_batch::DeviceBuffer<int32_t> d_part;             // n_seq x max_tiles x kWaves x kPartInts partial counts
     mld_batch::DescRing<DiSeq> ring;
 };
-
-namespace {
-
-void free_own(mld_depth_images* di) {
-    if (di->d_over) (void)hipFree(di->d_over);
-    if (di->d_part) (void)hipFree(di->d_part);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -898,15 +889,12 @@ mld_depth_images* mld_depth_images_create(mld_ctx* ctx, int n_seq, const mld_par
         return nullptr;
     };
     const char* bad = refusal();
+    std::string why;
+    int code = MLD_OK;
     if (!bad) {  // (what is refused with a status of its own; the context has not been looked at yet)
-        std::string why;
-        const int code = refuse_config(*params, *camera, T_cam_lidar, n_seq, why);
-        if (code != MLD_OK) {
-            std::snprintf(g_error, sizeof(g_error), "mld_depth_images_create: %s", why.c_str());
-            if (status_out) *status_out = code;
-            return nullptr;
-        }
-        if (!ctx) bad = "mld_depth_images_create: null context";  // (the last refusal: everything else was judged without it)
+        code = refuse_config(*params, *camera, T_cam_lidar, n_seq, why);
+        // (the last refusal: everything else was judged without it)
+        if (code == MLD_OK && !ctx) bad = "mld_depth_images_create: null context";
     }
     auto init = [&](mld_depth_images* di) -> int {
         di->n_seq = n_seq;
@@ -918,14 +906,16 @@ mld_depth_images* mld_depth_images_create(mld_ctx* ctx, int n_seq, const mld_par
         di->lds_bytes = (size_t)di->calib.cap * 28;
         di->max_tiles = tiles_of(camera->width, camera->height);
         const size_t waves = (size_t)n_seq * (size_t)di->max_tiles * kWaves;
-        MLD_HIP(di, hipMalloc((void**)&di->d_over, waves * kRowsPerWave * sizeof(unsigned long long)));
-        MLD_HIP(di, hipMalloc((void**)&di->d_part, waves * kPartInts * sizeof(int32_t)));
+        int rc;
+        if ((rc = di->d_over.allocate(di, waves * kRowsPerWave))) return rc;
+        if ((rc = di->d_part.allocate(di, waves * kPartInts))) return rc;
         return di->ring.allocate(di, n_seq);
     };
-    return mld_batch::create_object<mld_depth_images>(g_error, "mld_depth_images_create", bad, ctx, status_out, init, free_own);
+    return mld_batch::create_object<mld_depth_images>(g_error, "mld_depth_images_create", bad, ctx, status_out, init, code,
+                                                      why.c_str());
 }
 
-void mld_depth_images_destroy(mld_depth_images* di) { mld_batch::destroy_object(di, free_own); }
+void mld_depth_images_destroy(mld_depth_images* di) { mld_batch::destroy_object(di); }
 
 const char* mld_depth_images_last_error(const mld_depth_images* di) { return di ? di->err.c_str() : g_error; }
 
@@ -1012,12 +1002,12 @@ int mld_depth_images_render_device(mld_depth_images* di, const int32_t* const* m
     const int rc = di->ring.upload(di);
     if (rc) return rc;
     const unsigned blocks = (unsigned)((int64_t)S * tiles);
-    hipLaunchKernelGGL(k_depth_image_lane, dim3(blocks), dim3(kBlock), 0, di->stream, di->ring.d_desc, c, call, di->d_over, di->d_part);
+    hipLaunchKernelGGL(k_depth_image_lane, dim3(blocks), dim3(kBlock), 0, di->stream, di->ring.d_desc.get(), c, call, di->d_over.get(), di->d_part.get());
     MLD_HIP(di, hipGetLastError());
-    hipLaunchKernelGGL(k_depth_image_coop, dim3(blocks * kWaves), dim3(kWave), di->lds_bytes, di->stream, di->ring.d_desc, c, call,
-                       di->d_over, di->d_part);
+    hipLaunchKernelGGL(k_depth_image_coop, dim3(blocks * kWaves), dim3(kWave), di->lds_bytes, di->stream, di->ring.d_desc.get(), c, call,
+                       di->d_over.get(), di->d_part.get());
     MLD_HIP(di, hipGetLastError());
-    hipLaunchKernelGGL(k_depth_image_finish, dim3((unsigned)S), dim3(kBlock), 0, di->stream, di->ring.d_desc, call, di->d_part);
+    hipLaunchKernelGGL(k_depth_image_finish, dim3((unsigned)S), dim3(kBlock), 0, di->stream, di->ring.d_desc.get(), call, di->d_part.get());
     MLD_HIP(di, hipGetLastError());
     return MLD_OK;
 }

@@ -228,12 +228,6 @@ struct mld_labels : mld_batch::Object {
     mld_batch::DescRing<LbSeq> ring;
 };
 
-namespace {
-
-void free_own(mld_labels*) {}  // (the ring is all it has)
-
-}  // namespace
-
 extern "C" {
 
 mld_labels* mld_labels_create(mld_ctx* ctx, int n_seq, int* status_out) {
@@ -247,10 +241,10 @@ mld_labels* mld_labels_create(mld_ctx* ctx, int n_seq, int* status_out) {
         lb->n_seq = n_seq;
         return lb->ring.allocate(lb, n_seq);
     };
-    return mld_batch::create_object<mld_labels>(g_error, "mld_labels_create", refusal(), ctx, status_out, init, free_own);
+    return mld_batch::create_object<mld_labels>(g_error, "mld_labels_create", refusal(), ctx, status_out, init);
 }
 
-void mld_labels_destroy(mld_labels* lb) { mld_batch::destroy_object(lb, free_own); }
+void mld_labels_destroy(mld_labels* lb) { mld_batch::destroy_object(lb); }
 
 const char* mld_labels_last_error(const mld_labels* lb) { return lb ? lb->err.c_str() : g_error; }
 
@@ -298,9 +292,9 @@ int mld_labels_assign_device(mld_labels* lb, const uint8_t* const* label_image_d
     if (rc) return rc;
     const LbGeom g{rows, cols, row_stride_bytes, hw, hh};
     if (row_shape)
-        hipLaunchKernelGGL(k_labels_row, dim3((unsigned)blocks), dim3(kBlock), 0, lb->stream, lb->ring.d_desc, S, g);
+        hipLaunchKernelGGL(k_labels_row, dim3((unsigned)blocks), dim3(kBlock), 0, lb->stream, lb->ring.d_desc.get(), S, g);
     else
-        hipLaunchKernelGGL(k_labels_wave, dim3((unsigned)blocks), dim3(kBlock), 0, lb->stream, lb->ring.d_desc, S, g);
+        hipLaunchKernelGGL(k_labels_wave, dim3((unsigned)blocks), dim3(kBlock), 0, lb->stream, lb->ring.d_desc.get(), S, g);
     MLD_HIP(lb, hipGetLastError());
     return MLD_OK;
 }

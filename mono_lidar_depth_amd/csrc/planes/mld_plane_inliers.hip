@@ -268,20 +268,18 @@ int allocate(mld_plane_inliers* pi) {
     return pi->scratch.allocate(pi, pi->n_seq, pi->max_points, kChunk, 2, pi->calib.use != 0);
 }
 
-void free_own(mld_plane_inliers* pi) { pi->scratch.release(); }
-
 template <int kStride>
 void launch_all(mld_plane_inliers* pi, int chunks, bool any_list, mld_plane_inlier_counts* counts) {
     const unsigned S = (unsigned)pi->n_seq;
     const CompactScratch& cs = pi->scratch;
     if (chunks > 0)
-        hipLaunchKernelGGL(k_pi_pass<kStride>, dim3(S, (unsigned)chunks), dim3(kBlock), 0, pi->stream, pi->ring.d_desc, pi->calib,
-                           cs.d_gm, cs.groups_per_seq, cs.d_cpre, cs.chunks_per_seq);
-    hipLaunchKernelGGL(k_pi_scan, dim3(S), dim3(256), 0, pi->stream, pi->ring.d_desc, (int)pi->calib.use, cs.d_cpre,
+        hipLaunchKernelGGL(k_pi_pass<kStride>, dim3(S, (unsigned)chunks), dim3(kBlock), 0, pi->stream, pi->ring.d_desc.get(), pi->calib,
+                           cs.d_gm.get(), cs.groups_per_seq, cs.d_cpre.get(), cs.chunks_per_seq);
+    hipLaunchKernelGGL(k_pi_scan, dim3(S), dim3(256), 0, pi->stream, pi->ring.d_desc.get(), (int)pi->calib.use, cs.d_cpre.get(),
                        cs.chunks_per_seq, reinterpret_cast<long long*>(counts));
     if (chunks > 0 && any_list)
-        hipLaunchKernelGGL(k_pi_write<kStride>, dim3(S, (unsigned)chunks), dim3(kBlock), 0, pi->stream, pi->ring.d_desc, pi->calib,
-                           cs.d_gm, cs.groups_per_seq, cs.d_cpre, cs.chunks_per_seq);
+        hipLaunchKernelGGL(k_pi_write<kStride>, dim3(S, (unsigned)chunks), dim3(kBlock), 0, pi->stream, pi->ring.d_desc.get(), pi->calib,
+                           cs.d_gm.get(), cs.groups_per_seq, cs.d_cpre.get(), cs.chunks_per_seq);
 }
 
 }  // namespace
@@ -307,10 +305,10 @@ mld_plane_inliers* mld_plane_inliers_create(mld_ctx* ctx, int n_seq, int64_t max
         pi->calib.use = params->ransac_plane_use_camx_treshold ? 1 : 0;
         return allocate(pi);
     };
-    return mld_batch::create_object<mld_plane_inliers>(g_error, "mld_plane_inliers_create", refusal(), ctx, status_out, init, free_own);
+    return mld_batch::create_object<mld_plane_inliers>(g_error, "mld_plane_inliers_create", refusal(), ctx, status_out, init);
 }
 
-void mld_plane_inliers_destroy(mld_plane_inliers* pi) { mld_batch::destroy_object(pi, free_own); }
+void mld_plane_inliers_destroy(mld_plane_inliers* pi) { mld_batch::destroy_object(pi); }
 
 const char* mld_plane_inliers_last_error(const mld_plane_inliers* pi) { return pi ? pi->err.c_str() : g_error; }
 

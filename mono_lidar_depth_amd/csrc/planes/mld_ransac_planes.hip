@@ -623,20 +623,18 @@ int allocate(mld_ransac_planes* rp) {
     return MLD_OK;
 }
 
-void free_own(mld_ransac_planes* rp) { rp->scratch.release(); }
-
 template <int kStride>
 void launch_all(mld_ransac_planes* rp, int chunks, mld_ransac_plane_result* res) {
     const unsigned S = (unsigned)rp->n_seq;
     const CompactScratch& cs = rp->scratch;
     if (rp->P.pass) {
         if (chunks > 0)
-            hipLaunchKernelGGL(k_rp_pass<kStride>, dim3(S, (unsigned)chunks), dim3(kPassBlock), 0, rp->stream, rp->ring.d_desc,
-                               rp->P.lo, rp->P.hi, cs.d_gm, cs.groups_per_seq, cs.d_cpre, cs.chunks_per_seq);
-        hipLaunchKernelGGL(k_rp_scan, dim3(S), dim3(256), 0, rp->stream, rp->ring.d_desc, cs.d_cpre, cs.chunks_per_seq);
+            hipLaunchKernelGGL(k_rp_pass<kStride>, dim3(S, (unsigned)chunks), dim3(kPassBlock), 0, rp->stream, rp->ring.d_desc.get(),
+                               rp->P.lo, rp->P.hi, cs.d_gm.get(), cs.groups_per_seq, cs.d_cpre.get(), cs.chunks_per_seq);
+        hipLaunchKernelGGL(k_rp_scan, dim3(S), dim3(256), 0, rp->stream, rp->ring.d_desc.get(), cs.d_cpre.get(), cs.chunks_per_seq);
     }
-    hipLaunchKernelGGL(k_rp_estimate<kStride>, dim3(S), dim3(kThreads), kLdsBytes, rp->stream, rp->ring.d_desc, rp->P, cs.d_gm,
-                       cs.groups_per_seq, cs.d_cpre, cs.chunks_per_seq, res);
+    hipLaunchKernelGGL(k_rp_estimate<kStride>, dim3(S), dim3(kThreads), kLdsBytes, rp->stream, rp->ring.d_desc.get(), rp->P, cs.d_gm.get(),
+                       cs.groups_per_seq, cs.d_cpre.get(), cs.chunks_per_seq, res);
 }
 
 }  // namespace
@@ -670,11 +668,10 @@ mld_ransac_planes* mld_ransac_planes_create(mld_ctx* ctx, int n_seq, int64_t max
         P.hi = (float)params->ransac_plane_max_z;
         return allocate(rp);
     };
-    return mld_batch::create_object<mld_ransac_planes>(g_error, "mld_ransac_planes_create", refusal(), ctx, status_out, init,
-                                                       free_own);
+    return mld_batch::create_object<mld_ransac_planes>(g_error, "mld_ransac_planes_create", refusal(), ctx, status_out, init);
 }
 
-void mld_ransac_planes_destroy(mld_ransac_planes* rp) { mld_batch::destroy_object(rp, free_own); }
+void mld_ransac_planes_destroy(mld_ransac_planes* rp) { mld_batch::destroy_object(rp); }
 
 const char* mld_ransac_planes_last_error(const mld_ransac_planes* rp) { return rp ? rp->err.c_str() : g_error; }
 

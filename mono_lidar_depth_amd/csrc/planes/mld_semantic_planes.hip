@@ -287,24 +287,18 @@ struct mld_semantic_planes : mld_batch::Object {
     int64_t max_points = 0;
     long long groups_per_seq = 0;
     SpCalib calib{};
-    GroupSums* d_groups = nullptr;
-    float* d_first = nullptr;  // the first plane of every sequence
+    mld_batch::DeviceBuffer<GroupSums> d_groups;
+    mld_batch::DeviceBuffer<float> d_first;  // the first plane of every sequence
     mld_batch::DescRing<SpSeq> ring;
 };
 
 namespace {
 
 int allocate(mld_semantic_planes* sp) {
-    const int rc = sp->ring.allocate(sp, sp->n_seq);
-    if (rc) return rc;
-    MLD_HIP(sp, hipMalloc((void**)&sp->d_groups, (size_t)sp->n_seq * (size_t)sp->groups_per_seq * sizeof(GroupSums)));
-    MLD_HIP(sp, hipMalloc((void**)&sp->d_first, (size_t)sp->n_seq * 4 * sizeof(float)));
-    return MLD_OK;
-}
-
-void free_own(mld_semantic_planes* sp) {
-    if (sp->d_groups) (void)hipFree(sp->d_groups);
-    if (sp->d_first) (void)hipFree(sp->d_first);
+    int rc;
+    if ((rc = sp->ring.allocate(sp, sp->n_seq))) return rc;
+    if ((rc = sp->d_groups.allocate(sp, (size_t)sp->n_seq * (size_t)sp->groups_per_seq))) return rc;
+    return sp->d_first.allocate(sp, (size_t)sp->n_seq * 4);
 }
 
 template <int kStride>
@@ -313,15 +307,15 @@ void launch_all(mld_semantic_planes* sp, int chunks, const SpGeom& g, const Labe
     const int S = sp->n_seq;
     const dim3 stream_grid((unsigned)S, (unsigned)chunks), fit_grid((unsigned)S);
     if (chunks > 0)
-        hipLaunchKernelGGL(k_sp_candidates<kStride>, stream_grid, dim3(kBlock), 0, sp->stream, sp->ring.d_desc, sp->calib, g, ls,
-                           sp->d_groups, sp->groups_per_seq);
-    hipLaunchKernelGGL(k_sp_fit<0>, fit_grid, dim3(kPartials), 0, sp->stream, sp->ring.d_desc, sp->d_groups, sp->groups_per_seq,
-                       sp->d_first, res);
+        hipLaunchKernelGGL(k_sp_candidates<kStride>, stream_grid, dim3(kBlock), 0, sp->stream, sp->ring.d_desc.get(), sp->calib, g, ls,
+                           sp->d_groups.get(), sp->groups_per_seq);
+    hipLaunchKernelGGL(k_sp_fit<0>, fit_grid, dim3(kPartials), 0, sp->stream, sp->ring.d_desc.get(), sp->d_groups.get(), sp->groups_per_seq,
+                       sp->d_first.get(), res);
     if (chunks > 0)
-        hipLaunchKernelGGL(k_sp_select<kStride>, stream_grid, dim3(kBlock), 0, sp->stream, sp->ring.d_desc, sp->d_first, res, thr,
-                           sp->d_groups, sp->groups_per_seq);
-    hipLaunchKernelGGL(k_sp_fit<1>, fit_grid, dim3(kPartials), 0, sp->stream, sp->ring.d_desc, sp->d_groups, sp->groups_per_seq,
-                       sp->d_first, res);
+        hipLaunchKernelGGL(k_sp_select<kStride>, stream_grid, dim3(kBlock), 0, sp->stream, sp->ring.d_desc.get(), sp->d_first.get(), res, thr,
+                           sp->d_groups.get(), sp->groups_per_seq);
+    hipLaunchKernelGGL(k_sp_fit<1>, fit_grid, dim3(kPartials), 0, sp->stream, sp->ring.d_desc.get(), sp->d_groups.get(), sp->groups_per_seq,
+                       sp->d_first.get(), res);
 }
 
 }  // namespace
@@ -349,11 +343,10 @@ mld_semantic_planes* mld_semantic_planes_create(mld_ctx* ctx, int n_seq, int64_t
         sp->calib.cv = camera->principal_point_y;
         return allocate(sp);
     };
-    return mld_batch::create_object<mld_semantic_planes>(g_error, "mld_semantic_planes_create", refusal(), ctx, status_out, init,
-                                                         free_own);
+    return mld_batch::create_object<mld_semantic_planes>(g_error, "mld_semantic_planes_create", refusal(), ctx, status_out, init);
 }
 
-void mld_semantic_planes_destroy(mld_semantic_planes* sp) { mld_batch::destroy_object(sp, free_own); }
+void mld_semantic_planes_destroy(mld_semantic_planes* sp) { mld_batch::destroy_object(sp); }
 
 const char* mld_semantic_planes_last_error(const mld_semantic_planes* sp) { return sp ? sp->err.c_str() : g_error; }
 

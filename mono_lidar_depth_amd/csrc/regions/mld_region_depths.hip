@@ -417,12 +417,6 @@ struct mld_region_depths : mld_batch::Object {
     mld_batch::DescRing<RgSeq> ring;
 };
 
-namespace {
-
-void free_own(mld_region_depths*) {}  // (the ring is all the object allocates)
-
-}  // namespace
-
 extern "C" {
 
 mld_region_depths* mld_region_depths_create(mld_ctx* ctx, int n_seq, int64_t max_boxes, const mld_params* params,
@@ -436,9 +430,9 @@ mld_region_depths* mld_region_depths_create(mld_ctx* ctx, int n_seq, int64_t max
         return nullptr;
     };
     const char* bad = refusal();
+    const char* why = nullptr;
+    int code = MLD_ERR_INVALID_ARG;
     if (!bad) {
-        const char* why = nullptr;
-        int code = MLD_ERR_INVALID_ARG;
         const double bw = params->histogram_segmentation_bin_witdh;
         if (!std::isfinite(bw) || !(bw > 0.0)) {
             why = "histogram_segmentation_bin_witdh must be finite and > 0";
@@ -451,12 +445,7 @@ mld_region_depths* mld_region_depths_create(mld_ctx* ctx, int n_seq, int64_t max
             why = "n_seq sequences of max_boxes boxes need more than 2^31 - 1 blocks";
             code = MLD_ERR_CAPACITY;
         }
-        if (why) {
-            std::snprintf(g_error, sizeof(g_error), "mld_region_depths_create: %s", why);
-            if (status_out) *status_out = code;
-            return nullptr;
-        }
-        if (!ctx) bad = "mld_region_depths_create: null context";
+        if (!why && !ctx) bad = "mld_region_depths_create: null context";
     }
     auto init = [&](mld_region_depths* rd) -> int {
         rd->n_seq = n_seq;
@@ -474,10 +463,11 @@ mld_region_depths* mld_region_depths_create(mld_ctx* ctx, int n_seq, int64_t max
 #endif
         return rd->ring.allocate(rd, n_seq);
     };
-    return mld_batch::create_object<mld_region_depths>(g_error, "mld_region_depths_create", bad, ctx, status_out, init, free_own);
+    return mld_batch::create_object<mld_region_depths>(g_error, "mld_region_depths_create", bad, ctx, status_out, init,
+                                                       why ? code : MLD_OK, why);
 }
 
-void mld_region_depths_destroy(mld_region_depths* rd) { mld_batch::destroy_object(rd, free_own); }
+void mld_region_depths_destroy(mld_region_depths* rd) { mld_batch::destroy_object(rd); }
 
 const char* mld_region_depths_last_error(const mld_region_depths* rd) { return rd ? rd->err.c_str() : g_error; }
 
@@ -536,7 +526,7 @@ int mld_region_depths_collect_device(mld_region_depths* rd, const int32_t* const
     MLD_HIP(rd, hipSetDevice(rd->device));
     const int rc = rd->ring.upload(rd);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_region_depths, dim3((unsigned)((int64_t)S * per_seq)), dim3(kBlock), 0, rd->stream, rd->ring.d_desc, rd->calib,
+    hipLaunchKernelGGL(k_region_depths, dim3((unsigned)((int64_t)S * per_seq)), dim3(kBlock), 0, rd->stream, rd->ring.d_desc.get(), rd->calib,
                        (int)per_seq);
     MLD_HIP(rd, hipGetLastError());
     return MLD_OK;

@@ -230,24 +230,17 @@ struct mld_depth_reports : mld_batch::Object {
     int64_t max_features = 0;
     DrCam cam{};
     CompactScratch scratch;  // validity mask per group; valid features ahead of every chunk (+ the total)
-    int* d_hist = nullptr;   // kBins counts per chunk
+    mld_batch::DeviceBuffer<int> d_hist;  // kBins counts per chunk
     mld_batch::DescRing<DrSeq> ring;
 };
 
 namespace {
 
 int allocate(mld_depth_reports* dr) {
-    const int rc = dr->ring.allocate(dr, dr->n_seq);
-    if (rc) return rc;
-    const int rs = dr->scratch.allocate(dr, dr->n_seq, dr->max_features, kChunk, 1);
-    if (rs) return rs;
-    MLD_HIP(dr, hipMalloc((void**)&dr->d_hist, (size_t)dr->n_seq * (size_t)dr->scratch.chunks_per_seq * kBins * sizeof(int)));
-    return MLD_OK;
-}
-
-void free_own(mld_depth_reports* dr) {
-    dr->scratch.release();
-    if (dr->d_hist) (void)hipFree(dr->d_hist);
+    int rc;
+    if ((rc = dr->ring.allocate(dr, dr->n_seq))) return rc;
+    if ((rc = dr->scratch.allocate(dr, dr->n_seq, dr->max_features, kChunk, 1))) return rc;
+    return dr->d_hist.allocate(dr, (size_t)dr->n_seq * (size_t)dr->scratch.chunks_per_seq * kBins);
 }
 
 // The shared body of the two entry points.  a / b: the coordinate tables (LoadF64: uv and none; LoadF32: u and v).
@@ -316,13 +309,13 @@ int collect(mld_depth_reports* dr, const char* fn, const char* a_name, const voi
     const unsigned Su = (unsigned)S;
     const CompactScratch& cs = dr->scratch;
     if (chunks > 0)
-        hipLaunchKernelGGL(k_dr_pass<Load>, dim3(Su, chunks), dim3(kBlock), 0, dr->stream, dr->ring.d_desc, cs.d_gm,
-                           cs.groups_per_seq, cs.d_cpre, dr->d_hist, cs.chunks_per_seq);
-    hipLaunchKernelGGL(k_dr_scan, dim3(Su), dim3(256), 0, dr->stream, dr->ring.d_desc, cs.d_cpre, dr->d_hist, cs.chunks_per_seq,
+        hipLaunchKernelGGL(k_dr_pass<Load>, dim3(Su, chunks), dim3(kBlock), 0, dr->stream, dr->ring.d_desc.get(), cs.d_gm.get(),
+                           cs.groups_per_seq, cs.d_cpre.get(), dr->d_hist.get(), cs.chunks_per_seq);
+    hipLaunchKernelGGL(k_dr_scan, dim3(Su), dim3(256), 0, dr->stream, dr->ring.d_desc.get(), cs.d_cpre.get(), dr->d_hist.get(), cs.chunks_per_seq,
                        reinterpret_cast<long long*>(report_out_dev));
     if (chunks > 0 && any_points)
-        hipLaunchKernelGGL(k_dr_write<Load>, dim3(Su, chunks), dim3(kBlock), 0, dr->stream, dr->ring.d_desc, dr->cam, cs.d_gm,
-                           cs.groups_per_seq, cs.d_cpre, cs.chunks_per_seq);
+        hipLaunchKernelGGL(k_dr_write<Load>, dim3(Su, chunks), dim3(kBlock), 0, dr->stream, dr->ring.d_desc.get(), dr->cam, cs.d_gm.get(),
+                           cs.groups_per_seq, cs.d_cpre.get(), cs.chunks_per_seq);
     MLD_HIP(dr, hipGetLastError());
     return MLD_OK;
 }
@@ -351,10 +344,10 @@ mld_depth_reports* mld_depth_reports_create(mld_ctx* ctx, int n_seq, int64_t max
         dr->cam.cv = camera->principal_point_y;
         return allocate(dr);
     };
-    return mld_batch::create_object<mld_depth_reports>(g_error, "mld_depth_reports_create", refusal(), ctx, status_out, init, free_own);
+    return mld_batch::create_object<mld_depth_reports>(g_error, "mld_depth_reports_create", refusal(), ctx, status_out, init);
 }
 
-void mld_depth_reports_destroy(mld_depth_reports* dr) { mld_batch::destroy_object(dr, free_own); }
+void mld_depth_reports_destroy(mld_depth_reports* dr) { mld_batch::destroy_object(dr); }
 
 const char* mld_depth_reports_last_error(const mld_depth_reports* dr) { return dr ? dr->err.c_str() : g_error; }
 

@@ -275,8 +275,6 @@ struct mld_feature_traces : mld_batch::Object {
 
 namespace {
 
-void free_own(mld_feature_traces*) {}
-
 // Both collect calls: u_tab = uv (v_tab null) or u, v.
 template <bool kTracks>
 int collect(mld_feature_traces* ft, const char* fn, const void* const* u_tab, const float* const* v_tab, const int64_t* n_features,
@@ -362,7 +360,7 @@ int collect(mld_feature_traces* ft, const char* fn, const void* const* u_tab, co
     const int rc = ft->ring.upload(ft);
     if (rc) return rc;
     const unsigned gy = (unsigned)(longest < kMaxGridY ? longest : kMaxGridY);
-    hipLaunchKernelGGL(k_feature_trace<kTracks>, dim3((unsigned)S, gy), dim3(kWave), ft->lds_bytes, ft->stream, ft->ring.d_desc,
+    hipLaunchKernelGGL(k_feature_trace<kTracks>, dim3((unsigned)S, gy), dim3(kWave), ft->lds_bytes, ft->stream, ft->ring.d_desc.get(),
                        ft->calib, list_capacity);
     MLD_HIP(ft, hipGetLastError());
     return MLD_OK;
@@ -385,15 +383,9 @@ mld_feature_traces* mld_feature_traces_create(mld_ctx* ctx, int n_seq, int64_t m
         return nullptr;
     };
     const char* bad = refusal();
-    if (!bad) {  // (what is refused with a status of its own; still nothing of the context is used)
-        std::string why;
-        const int code = refuse_config(*params, *camera, T_cam_lidar, why);
-        if (code != MLD_OK) {
-            std::snprintf(g_error, sizeof(g_error), "mld_feature_traces_create: %s", why.c_str());
-            if (status_out) *status_out = code;
-            return nullptr;
-        }
-    }
+    std::string why;
+    // (what is refused with a status of its own; still nothing of the context is used)
+    const int code = bad ? MLD_OK : refuse_config(*params, *camera, T_cam_lidar, why);
     auto init = [&](mld_feature_traces* ft) {
         ft->n_seq = n_seq;
         ft->max_features = max_features;
@@ -401,10 +393,11 @@ mld_feature_traces* mld_feature_traces_create(mld_ctx* ctx, int n_seq, int64_t m
         ft->lds_bytes = (size_t)ft->calib.cap * 36 + sizeof(mld_feature_trace);
         return ft->ring.allocate(ft, n_seq);
     };
-    return mld_batch::create_object<mld_feature_traces>(g_error, "mld_feature_traces_create", bad, ctx, status_out, init, free_own);
+    return mld_batch::create_object<mld_feature_traces>(g_error, "mld_feature_traces_create", bad, ctx, status_out, init, code,
+                                                        why.c_str());
 }
 
-void mld_feature_traces_destroy(mld_feature_traces* ft) { mld_batch::destroy_object(ft, free_own); }
+void mld_feature_traces_destroy(mld_feature_traces* ft) { mld_batch::destroy_object(ft); }
 
 const char* mld_feature_traces_last_error(const mld_feature_traces* ft) { return ft ? ft->err.c_str() : g_error; }
 

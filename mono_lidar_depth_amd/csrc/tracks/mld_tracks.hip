@@ -767,7 +767,7 @@ struct LeaveOut {
 
 struct mld_tracks : mld_batch::Object {
     TrDev d{};
-    std::vector<void*> allocs;
+    std::vector<mld_batch::DeviceBuffer<unsigned char>> allocs;  // what the pointers of `d` and the two masks point into
     uint8_t* own_mask = nullptr;  // [n_seq][M]: the masks of a begin without is_new_out
     uint8_t* zero_mask = nullptr; // [M] zeros: the mask the depth call gets for a sequence without a previous frame
     mld_batch::DescRing<TrSeq> ring;
@@ -886,15 +886,15 @@ int queue_leaving(mld_tracks* tr, const LeaveOut& o, const uint8_t* mode) {
     if (rc) return rc;
     if ((rc = tr->ring.upload(tr))) return rc;
     if (blocks > 0) {
-        hipLaunchKernelGGL(k_tracks_leave_sums, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc,
+        hipLaunchKernelGGL(k_tracks_leave_sums, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc.get(),
                            tr->committed, tr->epoch);
         MLD_HIP(tr, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_tracks_leave_scan, dim3((unsigned)S), dim3(kScanWidth), 0, tr->stream, tr->d, tr->ring.d_desc,
+    hipLaunchKernelGGL(k_tracks_leave_scan, dim3((unsigned)S), dim3(kScanWidth), 0, tr->stream, tr->d, tr->ring.d_desc.get(),
                        static_cast<long long*>(o.record));
     MLD_HIP(tr, hipGetLastError());
     if (blocks > 0) {
-        hipLaunchKernelGGL(k_tracks_leave_write, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc,
+        hipLaunchKernelGGL(k_tracks_leave_write, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc.get(),
                            tr->committed);
         MLD_HIP(tr, hipGetLastError());
     }
@@ -903,10 +903,11 @@ int queue_leaving(mld_tracks* tr, const LeaveOut& o, const uint8_t* mode) {
 
 template <typename T>
 int dev_alloc(mld_tracks* tr, T** p, size_t count, bool zero) {
-    void* q = nullptr;
     const size_t bytes = std::max<size_t>(count * sizeof(T), 4);
-    MLD_HIP(tr, hipMalloc(&q, bytes));
-    tr->allocs.push_back(q);
+    tr->allocs.emplace_back();
+    const int rc = tr->allocs.back().allocate(tr, bytes);
+    if (rc) return rc;
+    void* q = tr->allocs.back().get();
     if (zero) MLD_HIP(tr, hipMemsetAsync(q, 0, bytes, tr->stream));
     *p = static_cast<T*>(q);
     return MLD_OK;
@@ -936,15 +937,11 @@ int allocate(mld_tracks* tr) {
     if ((rc = dev_alloc(tr, &tr->zero_mask, M, true))) return rc;
     if ((rc = tr->ring.allocate(tr, d.n_seq))) return rc;
     // (the table starts as zeros, like the rest of the store's memory)
-    MLD_HIP(tr, hipMemsetAsync(tr->ring.d_desc, 0, tr->ring.gen_bytes, tr->stream));
+    MLD_HIP(tr, hipMemsetAsync(tr->ring.d_desc.get(), 0, tr->ring.gen_bytes, tr->stream));
     const size_t total = std::max(S * M, S);
     hipLaunchKernelGGL(k_tracks_init, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, tr->stream, d);
     MLD_HIP(tr, hipGetLastError());
     return MLD_OK;
-}
-
-void free_own(mld_tracks* tr) {
-    for (void* p : tr->allocs) (void)hipFree(p);
 }
 
 }  // namespace
@@ -976,10 +973,10 @@ mld_tracks* mld_tracks_create(mld_ctx* ctx, int n_seq, int64_t max_tracks, int m
         tr->leave_mode.assign((size_t)n_seq, 0);
         return allocate(tr);
     };
-    return mld_batch::create_object<mld_tracks>(g_create_error, "mld_tracks_create", refusal(), ctx, status_out, init, free_own);
+    return mld_batch::create_object<mld_tracks>(g_create_error, "mld_tracks_create", refusal(), ctx, status_out, init);
 }
 
-void mld_tracks_destroy(mld_tracks* tr) { mld_batch::destroy_object(tr, free_own); }
+void mld_tracks_destroy(mld_tracks* tr) { mld_batch::destroy_object(tr); }
 
 const char* mld_tracks_last_error(const mld_tracks* tr) { return tr ? tr->err.c_str() : g_create_error; }
 
@@ -1007,7 +1004,7 @@ int mld_tracks_begin_device(mld_tracks* tr, const int32_t* const* ids, const int
     if ((rc = layout_blocks(tr, 1, &blocks, &blocks_prev))) return rc;
     if (blocks == 0) return MLD_OK;
     if ((rc = tr->ring.upload(tr))) return rc;
-    hipLaunchKernelGGL(k_tracks_lookup, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed,
+    hipLaunchKernelGGL(k_tracks_lookup, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc.get(), tr->committed,
                        tr->epoch);
     MLD_HIP(tr, hipGetLastError());
     return MLD_OK;
@@ -1042,11 +1039,11 @@ int mld_tracks_commit_device(mld_tracks* tr, const float* const* u_new, const fl
     int rc = layout_blocks(tr, 1, &blocks, &blocks_prev);
     if (rc) return rc;
     if ((rc = tr->ring.upload(tr))) return rc;
-    hipLaunchKernelGGL(k_tracks_release, dim3((unsigned)blocks_prev), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc,
+    hipLaunchKernelGGL(k_tracks_release, dim3((unsigned)blocks_prev), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc.get(),
                        tr->committed, tr->epoch);
     MLD_HIP(tr, hipGetLastError());
     if (blocks > 0) {
-        hipLaunchKernelGGL(k_tracks_commit, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc,
+        hipLaunchKernelGGL(k_tracks_commit, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc.get(),
                            1 - tr->committed);
         MLD_HIP(tr, hipGetLastError());
     }
@@ -1076,7 +1073,7 @@ int mld_tracks_export_device(mld_tracks* tr, float* const* fp_out, int32_t* cons
     if (rc) return rc;
     if (blocks == 0) return MLD_OK;
     if ((rc = tr->ring.upload(tr))) return rc;
-    hipLaunchKernelGGL(k_tracks_export, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed);
+    hipLaunchKernelGGL(k_tracks_export, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc.get(), tr->committed);
     MLD_HIP(tr, hipGetLastError());
     return MLD_OK;
 }
@@ -1108,11 +1105,11 @@ int mld_tracks_export_packed_device(mld_tracks* tr, float* const* fp_out, const 
     if (rc) return rc;
     if (blocks == 0) return MLD_OK;
     if ((rc = tr->ring.upload(tr))) return rc;
-    hipLaunchKernelGGL(k_tracks_pack_sums, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed);
+    hipLaunchKernelGGL(k_tracks_pack_sums, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc.get(), tr->committed);
     MLD_HIP(tr, hipGetLastError());
-    hipLaunchKernelGGL(k_tracks_pack_scan, dim3((unsigned)S), dim3(kScanWidth), 0, tr->stream, tr->d, tr->ring.d_desc);
+    hipLaunchKernelGGL(k_tracks_pack_scan, dim3((unsigned)S), dim3(kScanWidth), 0, tr->stream, tr->d, tr->ring.d_desc.get());
     MLD_HIP(tr, hipGetLastError());
-    hipLaunchKernelGGL(k_tracks_pack_write, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed);
+    hipLaunchKernelGGL(k_tracks_pack_write, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc.get(), tr->committed);
     MLD_HIP(tr, hipGetLastError());
     return MLD_OK;
 }
@@ -1219,10 +1216,10 @@ int import_packed(mld_tracks* tr, const char* fn, const uint8_t* select, const i
     if (blocks_reset > 0) {
         int rc = tr->ring.upload(tr);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_tracks_reset, dim3((unsigned)blocks_reset), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed);
+        hipLaunchKernelGGL(k_tracks_reset, dim3((unsigned)blocks_reset), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc.get(), tr->committed);
         MLD_HIP(tr, hipGetLastError());
         if (blocks > 0) {
-            hipLaunchKernelGGL(k_tracks_import, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed);
+            hipLaunchKernelGGL(k_tracks_import, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc.get(), tr->committed);
             MLD_HIP(tr, hipGetLastError());
         }
     }
@@ -1265,7 +1262,7 @@ int mld_tracks_counts(mld_tracks* tr, int64_t* counts_out) {
     MLD_HIP(tr, hipMemsetAsync(tr->d.feat, 0, (size_t)S * 2 * sizeof(unsigned long long), tr->stream));
     if (blocks > 0) {
         if ((rc = tr->ring.upload(tr))) return rc;
-        hipLaunchKernelGGL(k_tracks_count, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc, tr->committed);
+        hipLaunchKernelGGL(k_tracks_count, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->d, tr->ring.d_desc.get(), tr->committed);
         MLD_HIP(tr, hipGetLastError());
     }
     std::vector<unsigned int> cnt((size_t)S * 4);
@@ -1382,7 +1379,7 @@ static int tracklets_step(const char* fn, mld_ctx* ctx, mld_tracks* tr, int bank
         if ((rc = layout_blocks(tr, 1, &blocks, &blocks_prev))) return rc;
         if (blocks > 0) {
             if ((rc = tr->ring.upload(tr))) return rc;
-            hipLaunchKernelGGL(k_tracks_no_previous, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->ring.d_desc, S);
+            hipLaunchKernelGGL(k_tracks_no_previous, dim3((unsigned)blocks), dim3(kBlock), 0, tr->stream, tr->ring.d_desc.get(), S);
             MLD_HIP(tr, hipGetLastError());
         }
     }

@@ -41,6 +41,20 @@ def test_the_depth_path_header_restates_and_does_not_reach_into_the_depth_path()
     assert re.search(r"^SRC\s*:=.*batch/mld_batch_device\.h batch/mld_depth_path\.h", (CSRC / "Makefile").read_text(), flags=re.M)
 
 
+def test_the_batch_units_take_and_return_gpu_memory_through_the_object_header_only():
+    """Under the subdirectories of csrc/ only batch/mld_batch_object.h frees (and no unit has a free_own left), no unit
+    allocates by itself, and the shared types of that header have no release() to be called by hand."""
+    header = CSRC / "batch" / "mld_batch_object.h"
+    for path in CSRC.rglob("*"):
+        if not path.is_file() or path.parent == CSRC or path == header:
+            continue
+        text = path.read_text()
+        for word in ("hipFree", "hipHostFree", "free_own"):
+            assert word not in text, (path.name, word)
+        assert "hipMalloc(" not in text, path.name
+    assert not re.search(r"\brelease\s*\(", header.read_text())
+
+
 def test_the_functions_of_the_depth_path_header_exist_once_among_the_batch_units():
     """What the header took over is defined nowhere else under csrc/ outside the depth path's own files."""
     names = ("prefix_count", "uniform", "reduce_best", "wave_sum", "wave_max", "vsub", "vadd", "vscale", "vdivs", "vdot", "vsqnorm",
