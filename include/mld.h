@@ -1550,6 +1550,117 @@ int mld_region_depths_collect_device(mld_region_depths* rd, const int32_t* const
                                      mld_region_depth* const* record_out);
 
 /*
+ * Nearest-return depths of a batch — the main path on the k closest returns of a feature instead of the returns of a fixed
+ * rectangle, for n_seq independent sequences in one call.  A feature whose pixelarea_search window holds too few returns
+ * (MLD_RadiusSearchInsufficientPoints) gets no depth from the depth path; the reference's answer is neighbor_search_mode 1
+ * (parameters.yaml:5, NeighborFinderKdd: the nnSearch_count nearest returns, or all within radiusSearch_radius), which it
+ * ships unfinished.  This object is that search over the pixel map, as ONE rule of integers with both of its modes as
+ * corners: `count` nearest with a generous `radius`, or everything within `radius` with `count` at its maximum.  It runs on
+ * the arrays mld_projected_clouds_export_device wrote (pixel map, _pointIndex, camera-frame cloud).
+ *
+ * The neighbour rule, for a feature (u, v), radius R and count k:
+ *   centre cell   cx = (int)floor(clamp(u, -(R + 1), W + R)), cy = (int)floor(clamp(v, -(R + 1), H + R)), the clamp in f64
+ *                 ahead of the cast: a feature far outside the image has an empty disc.  A non-finite u or v gives no
+ *                 list, MLD_NEAREST_FLAG_NONFINITE_FEATURE and type 2.
+ *   candidates    the cells (x, y) with 0 <= x < W, 0 <= y < H and d2 = (x - cx)^2 + (y - cy)^2 <= R * R whose map value m
+ *                 is not -1, with 0 <= m < index_len and 0 <= index[m] < n_points.  A map value other than -1 that fails
+ *                 those bounds makes the cell EMPTY and sets MLD_NEAREST_FLAG_BAD_INPUT on the features whose disc holds
+ *                 it; no read leaves the arrays as the host tables size them.
+ *   the list      the candidates in ascending (d2, y, x); the first min(n_in_radius, k) of them.
+ * Two differences from the reference's finder, both deliberate: the pixel map holds ONE return per pixel (the first wins,
+ * NeighborFinderPixel.cpp:38-55), so this is a search over cells, not over the sub-pixel positions of all returns; and it
+ * is EXACT - the list is a function of the map alone - where FLANN's randomised kd-trees are approximate.
+ * The list's points, in that order, then go through the main path as mld_feature_traces runs it: n_nb <
+ * radiusSearch_count_min (compared as unsigned) gives type 2; the histogram segmentation with the 999 m clamp; the
+ * max-spanning triangle, or the first three points; the planarity test, the viewing ray through the exact (u, v) - not
+ * through the cell -, Hyperplane::Through, the orthogonality test, the thresholds, cut-behind-camera.  The road fallback
+ * does not run here.
+ *
+ * mld_nearest_depth, one per feature; every record is written completely on every call:
+ *   type          the main path's DepthResultType
+ *   n_in_radius   candidates in the disc: always complete, also beyond k
+ *   n_nb          entries of the list: min(n_in_radius, k)
+ *   n_seg         points the segmentation kept (n_nb with the histogram off; 0 where it failed or was not reached)
+ *   d2_first, d2_last   squared pixel distance of the first and of the last list entry; -1 without a list
+ *   nearest_orig  original index of the first list entry, or -1
+ *   flags         MLD_NEAREST_FLAG_BAD_INPUT 1, MLD_NEAREST_FLAG_NONFINITE_FEATURE 2
+ *   depth         -1 unless type == MLD_Success
+ *   nearest_z     camera z of the first list entry; NaN without one
+ *   corner_vis    visible indices of the triangle's corners, -1 without corners
+ *
+ * mld_nearest_depths_create: an object bound to `ctx` (its stream, its device) for calls of n_seq (1 .. 65536) sequences
+ *   of up to max_features (1 .. 16 777 216) features each, with radius in 1 .. MLD_NEAREST_MAX_RADIUS and count in
+ *   1 .. MLD_NEAREST_MAX_COUNT.  params and camera are copied: pass the values the context was created with.  No
+ *   transform is taken: nothing here reads it.  All memory is allocated here, none per call:
+ *     device  72 * n_seq bytes        (the descriptors)
+ *     pinned  16 * 72 * n_seq bytes   (the descriptor ring)
+ *   The sizes are checked before the context is looked at (n_seq, max_features, then radius and count:
+ *   MLD_ERR_INVALID_ARG with a text naming the argument), then the context, then params and camera (null), and then,
+ *   still without a use of the context:
+ *     MLD_ERR_UNSUPPORTED_MODE  do_use_PCA (the eigen-solve is a tolerance path, the records promise equality) and
+ *                               set_all_depths_to_zero
+ *     the refusals of mld_create for a parameter set and a camera, with its status codes and texts (neighbor_search_mode
+ *     other than 0 among them: the parameter set stays the one the context runs with)
+ *   Returns NULL on failure with the reason in *status_out (optional) and the text in
+ *   mld_nearest_depths_last_error(NULL).  Destroy the object before its context.
+ *
+ * mld_nearest_depths_collect_device (uv[s] 2 x n_features[s] f64 column-major) and
+ * mld_nearest_depths_collect_tracks_device (tracklet layer: u[s], v[s] f32; u = (double)truncf(u), likewise v, exactly as
+ * mld_feature_traces_collect_tracks_device): HOST tables of n_seq entries, consumed before the call returns; every array
+ * they name is DEVICE memory, naturally aligned for its element type (the records: 8 bytes).
+ *   n_features[s], map[s], index[s], index_len[s], cam[s], n_points[s]   as mld_feature_traces_collect_device takes them
+ *   record_out[s]       n_features[s] records
+ *   nb_out              optional (the table, or single entries): list_capacity x n_features[s] int32, feature i's row at
+ *                       i * list_capacity: the visible indices of the list in its order.  The first min(n_nb,
+ *                       list_capacity) entries of a row are written and nothing behind them is touched.
+ *   list_capacity       0 .. count; with 0 no list array is needed or written.
+ *   Asynchronous on the context's stream: no synchronisation, no host read of device data, no runtime call per sequence,
+ *   nothing allocated per call, no global atomics, no floating-point accumulation, two launches: the descriptor upload
+ *   and k_nearest_depths, ONE WAVEFRONT PER FEATURE.  The wavefront reads the disc in square stages of half size 4, 8, 16,
+ *   32, 64 (capped at radius) around the centre cell, only the new cells of each, and keeps a histogram of d2 in LDS; as
+ *   soon as a stage has shown count candidates within its inscribed circle the SEARCH is over - the cut-off distance
+ *   comes from the histogram, the candidates up to it are gathered from the small disc they lie in and ranked by
+ *   (d2, y, x) - and the cells of the later stages are only counted, for n_in_radius and BAD_INPUT.  The device arrays must
+ *   stay valid until the work has run.  Like a context, the object serves one call at a time.
+ *   MLD_ERR_INVALID_ARG with a text naming the function and the argument (mld_nearest_depths_last_error; "null object
+ *   (nd)" of NULL for a null object) on: a null object, a null table uv / u / v, n_features, map, index, index_len, cam,
+ *   n_points or record_out, a null uv / u / v, map or record_out array of a sequence with features (index, cam: where
+ *   index_len[s], n_points[s] > 0), a negative count, list_capacity outside 0 .. count, an int32 or float array that is
+ *   not 4-byte aligned, an f64 array or record_out that is not 8-byte aligned.  MLD_ERR_CAPACITY on n_features[s] beyond
+ *   max_features and on n_points[s] or index_len[s] beyond 8 388 607.
+ */
+#define MLD_NEAREST_MAX_RADIUS 64   /* pixels */
+#define MLD_NEAREST_MAX_COUNT 256   /* entries of a list */
+enum { MLD_NEAREST_FLAG_BAD_INPUT = 1, MLD_NEAREST_FLAG_NONFINITE_FEATURE = 2 };
+
+typedef struct mld_nearest_depth {      /* 64 bytes, 8-byte aligned */
+    int32_t type;           /* DepthResultType at the end of the main path */
+    int32_t n_in_radius;    /* candidates in the disc */
+    int32_t n_nb, n_seg;    /* entries of the list; those the segmentation kept */
+    int32_t d2_first, d2_last;  /* squared pixel distances of the first and the last list entry, -1 without a list */
+    int32_t nearest_orig;   /* original index of the first list entry, or -1 */
+    int32_t flags;          /* MLD_NEAREST_FLAG_* */
+    double  depth;          /* -1 unless type == MLD_Success */
+    double  nearest_z;      /* camera z of the first list entry, NaN without one */
+    int32_t corner_vis[3];  /* visible indices of the corners, -1 without corners */
+    int32_t pad_;
+} mld_nearest_depth;
+
+typedef struct mld_nearest_depths mld_nearest_depths;
+mld_nearest_depths* mld_nearest_depths_create(mld_ctx* ctx, int n_seq, int64_t max_features, int radius, int count,
+                                              const mld_params* params, const mld_camera* camera, int* status_out);
+void mld_nearest_depths_destroy(mld_nearest_depths* nd);
+const char* mld_nearest_depths_last_error(const mld_nearest_depths* nd);
+int mld_nearest_depths_collect_device(mld_nearest_depths* nd, const double* const* uv, const int64_t* n_features,
+                                      const int32_t* const* map, const int32_t* const* index, const int64_t* index_len,
+                                      const double* const* cam, const int64_t* n_points, int list_capacity,
+                                      mld_nearest_depth* const* record_out, int32_t* const* nb_out);
+int mld_nearest_depths_collect_tracks_device(mld_nearest_depths* nd, const float* const* u, const float* const* v,
+                                             const int64_t* n_features, const int32_t* const* map, const int32_t* const* index,
+                                             const int64_t* index_len, const double* const* cam, const int64_t* n_points,
+                                             int list_capacity, mld_nearest_depth* const* record_out, int32_t* const* nb_out);
+
+/*
  * Debug / parity getters (host buffers; each synchronises).
  *   mld_get_visible_count           -> _points_cs_image_visible.cols()         (DepthEstimator.cpp:192)
  *   mld_get_visible_image_points    -> getPointsCloudImageCs, 2 x Nvis col-major (:392-394)

@@ -204,6 +204,18 @@ class MldRegionDepth(C.Structure):
                 ("z_max", C.c_double), ("z_median", C.c_double), ("hist_lower", C.c_double), ("hist_higher", C.c_double)]
 
 
+# mld_nearest_depths: the bits of mld_nearest_depth::flags and the limits of radius and count (include/mld.h)
+MLD_NEAREST_FLAG_BAD_INPUT, MLD_NEAREST_FLAG_NONFINITE_FEATURE = 1, 2
+MLD_NEAREST_MAX_RADIUS, MLD_NEAREST_MAX_COUNT = 64, 256
+
+
+class MldNearestDepth(C.Structure):
+    """mld_nearest_depth (include/mld.h): one feature of mld_nearest_depths_collect_*_device, 64 bytes = 8 int64."""
+    _fields_ = [("type", C.c_int32), ("n_in_radius", C.c_int32), ("n_nb", C.c_int32), ("n_seg", C.c_int32),
+                ("d2_first", C.c_int32), ("d2_last", C.c_int32), ("nearest_orig", C.c_int32), ("flags", C.c_int32),
+                ("depth", C.c_double), ("nearest_z", C.c_double), ("corner_vis", C.c_int32 * 3), ("pad_", C.c_int32)]
+
+
 # Every symbol include/mld.h declares: (name, restype, argtypes)
 _P = C.POINTER
 _SIGNATURES = [
@@ -345,6 +357,14 @@ _SIGNATURES = [
     ("mld_region_depths_last_error", C.c_char_p, [C.c_void_p]),
     ("mld_region_depths_collect_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 2 + [_P(C.c_int64), _P(C.c_void_p),
                                                    _P(C.c_int64)] + [_P(C.c_void_p)] * 2 + [_P(C.c_int64), _P(C.c_void_p)]),
+    ("mld_nearest_depths_create", C.c_void_p, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, _P(MldParams), _P(MldCamera),
+                                               _P(C.c_int)]),
+    ("mld_nearest_depths_destroy", None, [C.c_void_p]),
+    ("mld_nearest_depths_last_error", C.c_char_p, [C.c_void_p]),
+    ("mld_nearest_depths_collect_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)] + [_P(C.c_void_p)] * 2 +
+     [_P(C.c_int64), _P(C.c_void_p), _P(C.c_int64), C.c_int] + [_P(C.c_void_p)] * 2),
+    ("mld_nearest_depths_collect_tracks_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 2 + [_P(C.c_int64)] +
+     [_P(C.c_void_p)] * 2 + [_P(C.c_int64), _P(C.c_void_p), _P(C.c_int64), C.c_int] + [_P(C.c_void_p)] * 2),
     ("mld_get_visible_count", C.c_int, [C.c_void_p, C.c_int, _P(C.c_int64)]),
     ("mld_get_visible_image_points", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
     ("mld_get_point_index", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),

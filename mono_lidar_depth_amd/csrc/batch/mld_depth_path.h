@@ -8,7 +8,9 @@
 // mld_batch_device.h and the public header.  No kernel, no state.
 //   device   the V3 algebra, smallest_eigvec3, Plane / plane_through, viewing_ray, intersect, apply_thresholds, finish_main
 //            (the B6 tail); window_bounds, far_from_plane, mask_bit; over a list of points in LDS worked on by one
-//            wavefront: gather_window, hist_segment, list_point, max_spanning_triangle, list_minmax_z
+//            wavefront: gather_window, hist_segment, list_point, max_spanning_triangle, list_minmax_z, and main_path, which
+//            strings the last four and finish_main together for a list from any neighbour search (the unit of the
+//            nearest-return depths runs it; k_feature_trace keeps its own sequence of the same calls)
 //   host     DepthCalib / build_calib, inverse3, camera_to_lidar, window_halves, window_cells, window_span, and what
 //            mld_create refuses of a parameter set, a camera and a transform, with its texts (refuse_*)
 // Every user is compiled without contraction.  The forms - values, references, a functor for what only one user stores -
@@ -470,6 +472,61 @@ __device__ __forceinline__ void list_minmax_z(int n, const PointList& L, int lan
     ib = uniform(ib);
     mn = (ia == kNone) ? kDblMax : L.z[ia];
     mx = (ib == kNone) ? -kDblMax : L.z[ib];
+}
+
+// The main path of CalculateDepth behind the neighbour search (DepthEstimator.cpp:680, :726-780, :903-1036) on the first
+// n_nb list entries, whichever search made the list: the count test, the histogram segmentation (the kept points
+// compacted in place), the corners, B6.  What a user may want of it comes back by value; every field is wave-uniform.
+struct MainPath {
+    int type;          // the result type at the end of the main path
+    int n_seg;         // points the segmentation kept; 0 without a segmentation that succeeded
+    int ci, cj, ck;    // the corners' positions in the segmented list, -1 without corners
+    double depth;      // -1 unless type == MLD_Success
+    double lower, higher;  // the borders of the chosen bin, -1 without one
+    Plane plane;       // Hyperplane::Through of the corners; NaN unless the path reached it
+    V3 c1, c2, c3;     // the corners; NaN without corners
+};
+// bin: n_nb ints of scratch (hist_segment).  keep(rank, i): what a user stores of the segmented point at `rank` that was
+// list entry i - called for every point of the segmented list, with the histogram off for every entry (rank == i).  A block
+// is one wavefront and every lane is here (barriers); the user's stores are visible when the function returns.
+template <typename Keep>
+__device__ __forceinline__ MainPath main_path(const DepthCalib& c, double u, double v, int n_nb, const PointList& L, int32_t* bin,
+                                              int lane, Keep keep) {
+    const double nan = __builtin_nan("");
+    MainPath r = {MLD_Unspecified, 0, -1, -1, -1, -1.0, -1.0, -1.0, {{nan, nan, nan}, nan}, {nan, nan, nan}, {nan, nan, nan},
+                  {nan, nan, nan}};
+    if ((unsigned)n_nb < c.countMin) {  // :680, compared as unsigned
+        r.type = MLD_RadiusSearchInsufficientPoints;
+        return r;
+    }
+    int ks = n_nb;  // CalculateDepthSegmentation (:726-780)
+    if (c.useHist) {
+        ks = hist_segment(c, n_nb, L, bin, lane, r.lower, r.higher, keep);
+    } else {
+        for (int i = lane; i < n_nb; i += kWave) keep(i, i);
+    }
+    __syncthreads();
+    if (ks < 0) {
+        r.type = MLD_HistogramNoLocalMax;
+        return r;
+    }
+    r.n_seg = ks;
+    int ci = 0, cj = 1, ck = 2;  // the corners (:915-926)
+    if (c.useTriMax) {
+        if (!max_spanning_triangle(ks, L, lane, ci, cj, ck)) {
+            r.type = MLD_TriangleNotPlanarInsufficientPoints;
+            return r;
+        }
+    } else if (ks < 3) {
+        r.type = MLD_HistogramNoLocalMax;  // :920-921
+        return r;
+    }
+    r.ci = ci, r.cj = cj, r.ck = ck;
+    r.c1 = list_point(L, ci), r.c2 = list_point(L, cj), r.c3 = list_point(L, ck);
+    double mn, mx;
+    list_minmax_z(ks, L, lane, mn, mx);
+    r.type = finish_main(c, u, v, r.c1, r.c2, r.c3, mn, mx, &r.plane, r.depth);
+    return r;
 }
 
 // ---- the host side: the calibration and what is refused of it

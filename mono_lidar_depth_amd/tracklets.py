@@ -236,7 +236,7 @@ def _result_tensor(t, shape, size, name):
 
 class _BatchObject:
     """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes, ProjectedClouds, DepthReports, PlaneInliers,
-    FeatureTraces, CoverageMaps, DepthImages and RegionDepths share: an object of the C-ABI (mld_<_NAME>_create / _destroy /
+    FeatureTraces, CoverageMaps, DepthImages, RegionDepths and NearestDepths share: an object of the C-ABI (mld_<_NAME>_create / _destroy /
     _last_error) on an estimator's context, its handle in the attribute named _HANDLE, the tensors of the calls that may
     still be queued, and one copy of every argument check.  The helpers, here and above:
 
@@ -1042,6 +1042,83 @@ class RegionDepths(_BatchObject):
         self._hold(pixel_map, index, cam, boxes, record, masks)
 
 
+class NearestDepths(_BatchObject):
+    """The main path on the `count` closest returns of a feature within `radius` pixels, for S sequences per call
+    (mld_nearest_depths_*, include/mld.h): an exact nearest-first search over the cells of the pixel map - ascending
+    (squared pixel distance, y, x) - in place of the fixed pixelarea_search rectangle, so that the list follows the local
+    density of the returns; then the count test, the histogram segmentation, the triangle and the intersection exactly as
+    FeatureTraces runs them, with the viewing ray through the feature itself.  The reference's neighbor_search_mode 1
+    (nnSearch_count nearest: `count` with a generous `radius`; radiusSearch_radius: `radius` with count MAX_COUNT).  No
+    road fallback.  It runs on the tensors ProjectedClouds.export wrote (pixel_map, index, cam).  collect() takes float64
+    uv, collect_tracks() the float32 u, v of the tracklet layer (truncated to the integer pixel).  `parameters` (default:
+    the estimator's) is copied at creation; do_use_PCA and set_all_depths_to_zero are refused.  Lists of S torch CUDA
+    tensors in and out; asynchronous on the estimator's stream.  Close it before its estimator."""
+
+    _NAME, _HANDLE = "nearest_depths", "_nd"
+    WORDS = 8  # int64 words of a record (capi.MldNearestDepth, 64 bytes)
+    DTYPE = np.dtype(capi.MldNearestDepth)
+    MAX_RADIUS, MAX_COUNT = capi.MLD_NEAREST_MAX_RADIUS, capi.MLD_NEAREST_MAX_COUNT
+
+    def __init__(self, estimator: DepthEstimator, n_seq: int, max_features: int, radius: int, count: int, parameters=None):
+        self.S, self.max_features, self.radius, self.count = int(n_seq), int(max_features), int(radius), int(count)
+        self._create(estimator, self.S, self.max_features, self.radius, self.count,
+                     *self._calibration(estimator, "parameters", "camera", parameters=parameters))
+
+    @classmethod
+    def records(cls, record) -> np.ndarray:
+        """A record tensor (int64 [n, 8]) as a NumPy record array with the fields of capi.MldNearestDepth (copies to
+        the host, which synchronises as usual)."""
+        return np.ascontiguousarray(record.cpu().numpy()).reshape(-1).view(cls.DTYPE)
+
+    def _collect(self, ns, feats, maps, index, cam, record, list_capacity, nb):
+        cap = int(list_capacity)
+        self._lengths(pixel_map=maps, index=index, cam=cam, record=record, nb=nb)
+        if not 0 <= cap <= self.count:
+            raise ValueError(f"list_capacity must be in 0 .. {self.count}")
+        for s, n in enumerate(ns):
+            if n == 0:  # (nothing of a sequence without features is looked at)
+                continue
+            _holds(maps[s], s, self.width * self.height, 4, "pixel_map", required=True)
+            _holds(index[s], s, 0, 4, "index")
+            _holds(cam[s], s, 0, 8, "cam")
+            _holds(record[s], s, self.WORDS * n, 8, "record", required=True)
+            if cap:
+                _holds(_at(nb, s), s, cap * n, 4, "nb")
+        vp = self._ptrs
+        fn = self._lib.mld_nearest_depths_collect_device if len(feats) == 1 else self._lib.mld_nearest_depths_collect_tracks_device
+        self._check(fn(self._nd, *[vp(t) for t in feats], self._i64(ns), vp(maps), vp(index), self._i64(_entries(t) for t in index),
+                       vp(cam), self._i64(_entries(t, 3) for t in cam), cap, vp(record), self._opt(nb)))
+        self._hold(*feats, maps, index, cam, record, nb)
+
+    def collect(self, uv, pixel_map, index, cam, record, list_capacity: int = 0, nb=None):
+        """uv: S contiguous float64 CUDA tensors [n, 2] (an entry None: a sequence without features); pixel_map, index,
+        cam: the S tensors each that ProjectedClouds.export wrote for the clouds (int32 [height, width], int32 of a
+        capacity that did not truncate, float64 [points, 3]); record: S int64 CUDA tensors of at least 8 * n entries (a
+        contiguous [n, 8]: capi.MldNearestDepth, see records()); nb: None, or S int32 CUDA tensors of at least
+        list_capacity * n entries (a contiguous [n, list_capacity]; single entries may be None): the visible indices of
+        the list, nearest first.  A row receives the first min(n_nb, list_capacity) entries; list_capacity is at most
+        `count`."""
+        self._lengths(uv=uv)
+        for s, t in enumerate(uv):
+            _holds(t, s, 0, 8, "uv")
+            if _entries(t) % 2:
+                raise ValueError(f"sequence {s}: uv must be a contiguous float64 tensor [n, 2]")
+        self._collect([_entries(t, 2) for t in uv], (uv,), pixel_map, index, cam, record, list_capacity, nb)
+
+    def collect_tracks(self, u, v, pixel_map, index, cam, record, list_capacity: int = 0, nb=None):
+        """As collect(), on the tensors of TrackletBatch.prepare_step() / prepare(): u, v (u_new, v_new): S float32 CUDA
+        tensors [n]."""
+        self._lengths(u=u, v=v)
+        for s, (a, b) in enumerate(zip(u, v)):
+            if (a is None) != (b is None):
+                raise ValueError(f"sequence {s}: u and v come together")
+            _holds(a, s, 0, 4, "u")
+            _holds(b, s, 0, 4, "v")
+            if _entries(b) != _entries(a):
+                raise ValueError(f"sequence {s}: u and v must be contiguous float32 tensors of one length")
+        self._collect([_entries(a) for a in u], (u, v), pixel_map, index, cam, record, list_capacity, nb)
+
+
 class TrackletBatch:
     """The tracklet layer for S independent sequences at once (mld_set_clouds_planes_range_device +
     mld_tracklets_depths_device): the estimator's frame slots are two banks of S slots, sequence s keeps its current
@@ -1068,7 +1145,8 @@ class TrackletBatch:
                    "feature_traces": (FeatureTraces, "attach_traces", ("max_tracks",)),
                    "coverage_maps": (CoverageMaps, "attach_coverage", ()),
                    "depth_image_maps": (DepthImages, "attach_depth_images", ()),
-                   "region_depth_boxes": (RegionDepths, "attach_region_depths", ())}
+                   "region_depth_boxes": (RegionDepths, "attach_region_depths", ()),
+                   "nearest_depth_lists": (NearestDepths, "attach_nearest_depths", ("max_tracks",))}
 
     def __init__(self, parameters, camera: CameraPinhole, transform_lidar_to_cam, n_seq: int, max_tracks: int,
                  device: int = 0, list_capacity=None):
@@ -1433,6 +1511,35 @@ class TrackletBatch:
         rd.collect(clouds["pixel_map"], clouds["index"], clouds["cam"], boxes, record, masks)
         self.est.orderTorchAfter()
         return record
+
+    def attach_nearest_depths(self, radius: int, count: int) -> NearestDepths:
+        """The nearest-return depths of the S sequences that nearest_depths() runs, for up to max_tracks tracks per
+        sequence: the `count` (1 .. NearestDepths.MAX_COUNT) closest returns within `radius` (1 .. NearestDepths.MAX_RADIUS)
+        pixels.  It takes the estimator's parameters as they are now."""
+        return self._attach("nearest_depth_lists", radius, count)
+
+    def nearest_depths(self, f, clouds, list_capacity: int = 0):
+        """A depth for the tracks of table `f` (prepare_step() / prepare()) from their nearest returns on this frame's
+        clouds - for the tracks whose search rectangle holds too few: NearestDepths.collect_tracks on the table's u_new,
+        v_new and on `clouds`, the dict projected_clouds(cam=True, pixel_map=True) returned for the same clouds with a
+        capacity that did not truncate.  Returns a dict with record (S int64 [n, 8]: capi.MldNearestDepth, see
+        NearestDepths.records()) and nb (S int32 [n, list_capacity]: a row holds the first min(n_nb, list_capacity)
+        visible indices of its list, the rest is not written; None with list_capacity 0).  No synchronisation: torch's
+        current stream is made to wait for the call; a host read synchronises as usual.  attach_nearest_depths() first."""
+        import torch
+        nd = self._attached("nearest_depth_lists", "nearest_depths")
+        if clouds.get("cam") is None or clouds.get("pixel_map") is None:
+            raise ValueError("clouds: projected_clouds(cam=True, pixel_map=True) of this frame")
+        u_new, v_new = f["features"]
+        dev = next((t.device for t in u_new if t is not None), torch.device("cuda", self.est._device))
+        ns = [_entries(t) for t in u_new]
+        cap = int(list_capacity)
+        out = {"record": [torch.empty((n, NearestDepths.WORDS), dtype=torch.int64, device=dev) for n in ns],
+               "nb": [torch.empty((n, cap), dtype=torch.int32, device=dev) for n in ns] if cap else None}
+        self.est._after_torch(*[t for t in u_new if t is not None][:1])
+        nd.collect_tracks(u_new, v_new, clouds["pixel_map"], clouds["index"], clouds["cam"], out["record"], cap, out["nb"])
+        self.est.orderTorchAfter()
+        return out
 
     def attach_labels(self) -> SemanticLabels:
         """The label assignment of the S sequences that labels() queues behind a step."""
