@@ -1661,6 +1661,92 @@ int mld_nearest_depths_collect_tracks_device(mld_nearest_depths* nd, const float
                                              int list_capacity, mld_nearest_depth* const* record_out, int32_t* const* nb_out);
 
 /*
+ * Merged sweeps of a batch — the last few lidar sweeps of n_seq independent sequences carried into the current lidar
+ * frame and concatenated, current sweep first, in one call.  Most features get no depth because too few returns lie
+ * around them (MLD_RadiusSearchInsufficientPoints); the usual remedy changes the cloud, not the search: the sweeps the
+ * sensor delivered just before, moved by the ego-motion the SLAM loop already has, projected together with the current
+ * one.  The pixel map keeps the FIRST return that lands in a cell (NeighborFinderPixel.cpp:38-55): with the current
+ * sweep in front its returns keep their cells and the older sweeps only fill empty ones, so the order of the output
+ * is part of the contract.  The merged cloud is a cloud as mld_set_clouds*_device takes it (16-byte records).
+ *
+ * The rule, for sequence s and sweep j (0: the current one) of n_sweeps, entry e = s * n_sweeps + j of the tables:
+ *   record      n[e] records of stride_bytes at pts_dev[e]: x, y, z at offsets 0, 4, 8; the intensity where
+ *               mld_pack_points_host takes it (offset 12 of a 16-byte record, 16 of a 32-byte one), as raw bits.
+ *   transform   T[e]: 12 doubles in HOST memory, a row-major 3x4 matrix from sweep j's lidar frame to the current one,
+ *               read before the call returns.  A NULL entry (a NULL table: every entry) is the identity: x, y, z are
+ *               taken bit for bit, the sign of a zero included.  Otherwise, with x, y, z promoted to double,
+ *                 x' = (float)(T[3] + (T[0] * x + (T[1] * y + T[2] * z)))      y', z' likewise from rows 1, 2
+ *               in exactly this operation order, without contraction.
+ *   dropped     NON-FINITE: one of x', y', z' is not finite.  OUT OF RANGE: r2 = x' * x' + (y' * y' + z' * z') in f32
+ *               fails lo2 <= r2 && r2 <= hi2, with lo2 = min_range * min_range and hi2 = max_range * max_range made
+ *               on the host in f32.  A record that is both counts as non-finite only.  min_range 0 with max_range
+ *               +inf gates nothing.
+ *   output      the kept records of sweep 0 in their order, then those of sweep 1, and so on, as packed 16-byte records
+ *               {x', y', z', intensity bits} in merged_out[s]; the first min(n_kept, capacity[s]) of them are written
+ *               and nothing behind them is touched.  The counts stay complete beyond the capacity.
+ *
+ * mld_sweep_merge_record, one per sequence, in DEVICE memory; every record is written completely on every call:
+ *   n_in            records of all sweeps
+ *   n_kept          n_in - n_nonfinite - n_out_of_range
+ *   n_written       min(n_kept, capacity[s])
+ *   n_nonfinite, n_out_of_range   the two reasons, each record under one
+ *   kept[j]         kept records of sweep j, complete also beyond the capacity; 0 at and beyond n_sweeps
+ *   flags           MLD_SWEEP_FLAG_TRUNCATED: n_kept > capacity[s]
+ *
+ * mld_sweep_merge_create: an object bound to `ctx` (its stream, its device) for calls of n_seq (1 .. 65536) sequences of
+ *   up to max_sweeps (1 .. MLD_SWEEP_MAX_SWEEPS) sweeps of up to max_points (1 .. 8 388 607) points each, with
+ *   max_sweeps * max_points <= 8 388 607: the merged cloud must fit the 23-bit point index of the pixel map.  All memory
+ *   is allocated here, none per call; with I = max_sweeps * max_points:
+ *     device  152 * max_sweeps * n_seq bytes        (the descriptors, one per sweep)
+ *             n_seq * (8 * ceil(I / 64) + 8 * (ceil(I / 1024) + 1) + 72) bytes   (kept mask per 64 items, two counts per
+ *                                                   1024 items, the totals)
+ *     pinned  16 * 152 * max_sweeps * n_seq bytes   (the descriptor ring)
+ *   The sizes are checked before the context is looked at, in the order n_seq, max_sweeps, max_points, their product
+ *   (MLD_ERR_INVALID_ARG with a text naming the argument), then the context.  Returns NULL on failure with the reason
+ *   in *status_out (optional) and the text in mld_sweep_merge_last_error(NULL).  Destroy the object before its context.
+ *
+ * mld_sweep_merge_run_device: HOST tables, consumed before the call returns; every array they name is DEVICE memory.
+ *   pts_dev, n, T   n_seq * n_sweeps entries (T: optional, as above); the records 4-byte aligned
+ *   capacity[s]     records merged_out[s] has room for
+ *   merged_out[s]   16 * capacity[s] bytes, 4-byte aligned; may be NULL where capacity[s] or the sequence's n_in is 0
+ *   sweep_out       optional (the table, or single entries): uint8 per written record, the sweep j it came from
+ *   orig_out        optional likewise: int32 per written record, its index within its sweep; 4-byte aligned
+ *   record_out_dev  n_seq records, 8-byte aligned
+ *   Asynchronous on the context's stream: no synchronisation, no host read of device data, no runtime call per
+ *   sequence, nothing allocated per call, no atomics, four launches: the descriptor upload, k_sm_pass (one load of 16
+ *   bytes per record, the transform, the tests; a 64-bit mask per 64 items and two drop counts per 1024), k_sm_scan (per
+ *   sequence: the prefixes, the kept records of every sweep) and k_sm_write (rank by popcount; only kept records below
+ *   the capacity are loaded and transformed again and stored whole; one more block per sequence writes the record).
+ *   The device arrays must stay valid until the work has run.  Like a context, the object serves one call at a time.
+ *   The arguments are judged in this order, before anything is queued: the object; n_sweeps; the tables pts_dev and n;
+ *   stride_bytes; min_range, max_range (each >= 0 and not NaN, min_range <= max_range); the tables capacity and
+ *   merged_out; record_out_dev and its alignment; then per sequence its sweeps in order (n, pts_dev), its capacity and
+ *   its output arrays.  MLD_ERR_INVALID_ARG with a text naming the function and the argument
+ *   (mld_sweep_merge_last_error; "null object (sm)" of NULL for a null object) on: a null object, n_sweeps outside
+ *   1 .. max_sweeps, a null table pts_dev, n, capacity or merged_out, a null record_out_dev, a stride other than 16 or
+ *   32, a bad range, a negative n or capacity, a null pts_dev of a sweep with points, a null merged_out of a sequence
+ *   with points and capacity, an array that is not aligned as said.  MLD_ERR_CAPACITY on n beyond max_points.
+ */
+#define MLD_SWEEP_MAX_SWEEPS 16
+enum { MLD_SWEEP_FLAG_TRUNCATED = 1 };
+
+typedef struct mld_sweep_merge_record {  /* 112 bytes, 8-byte aligned */
+    int64_t n_in, n_kept, n_written, n_nonfinite, n_out_of_range;
+    int32_t kept[MLD_SWEEP_MAX_SWEEPS];  /* per sweep, complete */
+    int32_t flags;                       /* MLD_SWEEP_FLAG_* */
+    int32_t pad_;
+} mld_sweep_merge_record;
+
+typedef struct mld_sweep_merge mld_sweep_merge;
+mld_sweep_merge* mld_sweep_merge_create(mld_ctx* ctx, int n_seq, int max_sweeps, int64_t max_points, int* status_out);
+void mld_sweep_merge_destroy(mld_sweep_merge* sm);
+const char* mld_sweep_merge_last_error(const mld_sweep_merge* sm);
+int mld_sweep_merge_run_device(mld_sweep_merge* sm, int n_sweeps, const void* const* pts_dev, const int64_t* n,
+                               int stride_bytes, const double* const* T, float min_range, float max_range,
+                               const int64_t* capacity, void* const* merged_out, uint8_t* const* sweep_out,
+                               int32_t* const* orig_out, mld_sweep_merge_record* record_out_dev);
+
+/*
  * Debug / parity getters (host buffers; each synchronises).
  *   mld_get_visible_count           -> _points_cs_image_visible.cols()         (DepthEstimator.cpp:192)
  *   mld_get_visible_image_points    -> getPointsCloudImageCs, 2 x Nvis col-major (:392-394)

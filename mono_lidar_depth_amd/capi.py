@@ -216,6 +216,18 @@ class MldNearestDepth(C.Structure):
                 ("depth", C.c_double), ("nearest_z", C.c_double), ("corner_vis", C.c_int32 * 3), ("pad_", C.c_int32)]
 
 
+# mld_sweep_merge: the bit of mld_sweep_merge_record::flags and the limit of max_sweeps (include/mld.h)
+MLD_SWEEP_FLAG_TRUNCATED = 1
+MLD_SWEEP_MAX_SWEEPS = 16
+
+
+class MldSweepMergeRecord(C.Structure):
+    """mld_sweep_merge_record (include/mld.h): one sequence of mld_sweep_merge_run_device, 112 bytes = 14 int64."""
+    _fields_ = [("n_in", C.c_int64), ("n_kept", C.c_int64), ("n_written", C.c_int64), ("n_nonfinite", C.c_int64),
+                ("n_out_of_range", C.c_int64), ("kept", C.c_int32 * MLD_SWEEP_MAX_SWEEPS), ("flags", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
 # Every symbol include/mld.h declares: (name, restype, argtypes)
 _P = C.POINTER
 _SIGNATURES = [
@@ -365,6 +377,11 @@ _SIGNATURES = [
      [_P(C.c_int64), _P(C.c_void_p), _P(C.c_int64), C.c_int] + [_P(C.c_void_p)] * 2),
     ("mld_nearest_depths_collect_tracks_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 2 + [_P(C.c_int64)] +
      [_P(C.c_void_p)] * 2 + [_P(C.c_int64), _P(C.c_void_p), _P(C.c_int64), C.c_int] + [_P(C.c_void_p)] * 2),
+    ("mld_sweep_merge_create", C.c_void_p, [C.c_void_p, C.c_int, C.c_int, C.c_int64, _P(C.c_int)]),
+    ("mld_sweep_merge_destroy", None, [C.c_void_p]),
+    ("mld_sweep_merge_last_error", C.c_char_p, [C.c_void_p]),
+    ("mld_sweep_merge_run_device", C.c_int, [C.c_void_p, C.c_int, _P(C.c_void_p), _P(C.c_int64), C.c_int, _P(C.c_void_p),
+                                             C.c_float, C.c_float, _P(C.c_int64)] + [_P(C.c_void_p)] * 3 + [C.c_void_p]),
     ("mld_get_visible_count", C.c_int, [C.c_void_p, C.c_int, _P(C.c_int64)]),
     ("mld_get_visible_image_points", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
     ("mld_get_point_index", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),

@@ -236,7 +236,7 @@ def _result_tensor(t, shape, size, name):
 
 class _BatchObject:
     """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes, ProjectedClouds, DepthReports, PlaneInliers,
-    FeatureTraces, CoverageMaps, DepthImages, RegionDepths and NearestDepths share: an object of the C-ABI (mld_<_NAME>_create / _destroy /
+    FeatureTraces, CoverageMaps, DepthImages, RegionDepths, NearestDepths and SweepMerge share: an object of the C-ABI (mld_<_NAME>_create / _destroy /
     _last_error) on an estimator's context, its handle in the attribute named _HANDLE, the tensors of the calls that may
     still be queued, and one copy of every argument check.  The helpers, here and above:
 
@@ -1119,6 +1119,76 @@ class NearestDepths(_BatchObject):
         self._collect([_entries(a) for a in u], (u, v), pixel_map, index, cam, record, list_capacity, nb)
 
 
+class SweepMerge(_BatchObject):
+    """The last few lidar sweeps of S sequences carried into the current lidar frame and concatenated, current sweep first
+    (mld_sweep_merge_*, include/mld.h - the transform's operation order and the two drop tests are stated there): every
+    record is transformed by its sweep's 3x4 matrix, dropped when the result is not finite or outside [min_range,
+    max_range], and the rest written as packed 16-byte records in the order (sweep, index within the sweep) - the order in
+    which the pixel map, whose cells keep their FIRST return, prefers the current sweep.  Up to max_sweeps sweeps of up to
+    max_points points each per sequence, max_sweeps * max_points <= 8 388 607.  Lists of torch CUDA tensors in and out;
+    asynchronous on the estimator's stream.  Close it before its estimator."""
+
+    _NAME, _HANDLE = "sweep_merge", "_sm"
+    WORDS = 14  # int64 words of a record (capi.MldSweepMergeRecord, 112 bytes)
+    DTYPE = np.dtype(capi.MldSweepMergeRecord)
+    MAX_SWEEPS = capi.MLD_SWEEP_MAX_SWEEPS
+
+    def __init__(self, estimator: DepthEstimator, n_seq: int, max_sweeps: int, max_points: int):
+        self.S, self.max_sweeps, self.max_points = int(n_seq), int(max_sweeps), int(max_points)
+        self._create(estimator, self.S, self.max_sweeps, self.max_points)
+
+    @classmethod
+    def records(cls, record) -> np.ndarray:
+        """A record tensor (int64 [S, 14]) as a NumPy record array with the fields of capi.MldSweepMergeRecord (copies
+        to the host, which synchronises as usual)."""
+        return np.ascontiguousarray(record.cpu().numpy()).reshape(-1).view(cls.DTYPE)
+
+    def merge(self, sweeps, transforms, capacity, merged, record, sweep_out=None, orig_out=None, min_range: float = 0.0,
+              max_range: float = float("inf")):
+        """sweeps: S lists of one length n_sweeps (1 .. max_sweeps), sweep 0 the current one, of contiguous float32 CUDA
+        tensors [n, 4] or [n, 8] of one width (an entry None: a sweep without points); transforms: None (identity
+        throughout), or S lists of n_sweeps entries, each None (identity: the coordinates bit for bit) or at least 12
+        float64 values, the row-major 3x4 matrix (a 4x4 passes) from that sweep's lidar frame to the current one;
+        capacity: S integers, or None (= the sequence's points, never truncated); merged: S float32 CUDA tensors of at
+        least 4 * min(capacity, points) entries (a contiguous [capacity, 4]; None where that is 0); record: an int64 CUDA
+        tensor [S, 14] that receives the records (capi.MldSweepMergeRecord, see records()); sweep_out: None, or S uint8
+        CUDA tensors of at least min(capacity, points) entries (single entries may be None): the sweep a written record
+        came from; orig_out: likewise int32: its index within its sweep.  Kept records at or beyond a sequence's
+        capacity are dropped, which the caller sees from the record (n_kept > n_written, MLD_SWEEP_FLAG_TRUNCATED)."""
+        self._lengths(sweeps=sweeps, transforms=transforms, capacity=capacity, merged=merged, sweep_out=sweep_out,
+                      orig_out=orig_out)
+        _result_tensor(record, (self.S, self.WORDS), 8, "record")
+        k = len(sweeps[0])
+        if any(len(row) != k for row in sweeps) or (transforms is not None and any(len(row) != k for row in transforms)):
+            raise ValueError("sweeps, transforms: one number of sweeps for all sequences")
+        if not 1 <= k <= self.max_sweeps:
+            raise ValueError(f"sweeps: 1 .. {self.max_sweeps} sweeps per sequence")
+        flat = [cl for row in sweeps for cl in row]
+        width, ns = _cloud_table(flat)
+        items = [sum(ns[s * k:(s + 1) * k]) for s in range(self.S)]
+        caps = _capacities(capacity, items)
+        for s, n in enumerate(items):
+            m = min(caps[s], n)
+            _holds(merged[s], s, 4 * m, 4, "merged", required=True)
+            _holds(_at(sweep_out, s), s, m, 1, "sweep_out")
+            _holds(_at(orig_out, s), s, m, 4, "orig_out")
+        mats, T = [], None
+        if transforms is not None:
+            for s, row in enumerate(transforms):
+                for t in row:
+                    a = None if t is None else np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1)[:12])
+                    if a is not None and a.size != 12:
+                        raise ValueError(f"sequence {s}: a transform holds at least 12 values (row-major 3x4)")
+                    mats.append(a)
+            T = (C.c_void_p * len(mats))(*[a.ctypes.data if a is not None else None for a in mats])
+        pts = (C.c_void_p * len(flat))(*[int(t.data_ptr()) if t is not None else None for t in flat])
+        self._check(self._lib.mld_sweep_merge_run_device(
+            self._sm, k, pts, (C.c_int64 * len(ns))(*ns), 4 * width, T, float(min_range), float(max_range), self._i64(caps),
+            self._ptrs(merged), self._opt(sweep_out), self._opt(orig_out), int(record.data_ptr())))
+        del mats  # (the matrices are consumed before the call returns)
+        self._hold(flat, merged, record, sweep_out, orig_out)
+
+
 class TrackletBatch:
     """The tracklet layer for S independent sequences at once (mld_set_clouds_planes_range_device +
     mld_tracklets_depths_device): the estimator's frame slots are two banks of S slots, sequence s keeps its current
@@ -1146,7 +1216,8 @@ class TrackletBatch:
                    "coverage_maps": (CoverageMaps, "attach_coverage", ()),
                    "depth_image_maps": (DepthImages, "attach_depth_images", ()),
                    "region_depth_boxes": (RegionDepths, "attach_region_depths", ()),
-                   "nearest_depth_lists": (NearestDepths, "attach_nearest_depths", ("max_tracks",))}
+                   "nearest_depth_lists": (NearestDepths, "attach_nearest_depths", ("max_tracks",)),
+                   "sweep_merger": (SweepMerge, "attach_sweep_merge", ())}
 
     def __init__(self, parameters, camera: CameraPinhole, transform_lidar_to_cam, n_seq: int, max_tracks: int,
                  device: int = 0, list_capacity=None):
@@ -1540,6 +1611,44 @@ class TrackletBatch:
         nd.collect_tracks(u_new, v_new, clouds["pixel_map"], clouds["index"], clouds["cam"], out["record"], cap, out["nb"])
         self.est.orderTorchAfter()
         return out
+
+    def attach_sweep_merge(self, max_sweeps: int, max_points: int) -> SweepMerge:
+        """The merge of up to max_sweeps lidar sweeps of up to max_points points each per sequence that merge_sweeps()
+        runs ahead of the projection (max_sweeps * max_points <= 8 388 607; 133 KB of scratch per sequence per million
+        points of the merged cloud)."""
+        return self._attach("sweep_merger", max_sweeps, max_points)
+
+    def merge_sweeps(self, sweeps, transforms, min_range: float = 0.0, max_range: float = float("inf"), sweep: bool = False,
+                     orig: bool = False):
+        """The current sweep of every sequence with its older sweeps behind it, all in the current lidar frame, ready for
+        the projection (prepare_step() / prepare(), projected_clouds(), mld_set_clouds*_device): SweepMerge.merge on
+        `sweeps` (S lists of n_sweeps float32 CUDA tensors [n, 4] or [n, 8], sweep 0 the current one) and `transforms`
+        (None, or S lists of n_sweeps entries, each None or the row-major 3x4 matrix into the current lidar frame), with a
+        capacity that never truncates.  Returns a dict with merged (S float32 [n_kept, 4], views of the tensors the call
+        wrote), n (the S host counts n_kept, which the projection takes from the host), record (the S records on the
+        host, capi.MldSweepMergeRecord) and, where asked for, sweep (S uint8 [n_kept]: the sweep a record came from)
+        and orig (S int32 [n_kept]: its index within its sweep).  One call on the GPU, then ONE device-to-host copy of
+        112 * S bytes and one synchronisation per batch: the projection takes its counts from the host.  torch's current
+        stream is made to wait for the call.  attach_sweep_merge() first."""
+        import torch
+        sm = self._attached("sweep_merger", "merge_sweeps")
+        if len(sweeps) != self.S:
+            raise ValueError(f"sweeps: expected {self.S} entries, one per sequence")
+        flat = [c for row in sweeps for c in row if c is not None]
+        dev = flat[0].device if flat else torch.device("cuda", self.est._device)
+        items = [sum(int(c.shape[0]) for c in row if c is not None) for row in sweeps]
+        merged = [torch.empty((n, 4), dtype=torch.float32, device=dev) for n in items]
+        record = torch.empty((self.S, SweepMerge.WORDS), dtype=torch.int64, device=dev)
+        sw = [torch.empty(n, dtype=torch.uint8, device=dev) for n in items] if sweep else None
+        og = [torch.empty(n, dtype=torch.int32, device=dev) for n in items] if orig else None
+        self.est._after_torch(*flat[:1])
+        sm.merge(sweeps, transforms, None, merged, record, sw, og, min_range, max_range)
+        self.est.orderTorchAfter()
+        host = SweepMerge.records(record)  # (the copy waits for the call)
+        ns = [int(k) for k in host["n_kept"]]
+        return {"merged": [m[:k] for m, k in zip(merged, ns)], "n": ns, "record": host,
+                "sweep": [t[:k] for t, k in zip(sw, ns)] if sweep else None,
+                "orig": [t[:k] for t, k in zip(og, ns)] if orig else None}
 
     def attach_labels(self) -> SemanticLabels:
         """The label assignment of the S sequences that labels() queues behind a step."""
