@@ -9,10 +9,13 @@
 //   device   the V3 algebra, smallest_eigvec3, Plane / plane_through, viewing_ray, intersect, apply_thresholds, finish_main
 //            (the B6 tail); window_bounds, far_from_plane, mask_bit; over a list of points in LDS worked on by one
 //            wavefront: gather_window, hist_segment, list_point, max_spanning_triangle, list_minmax_z, and main_path, which
-//            strings the last four and finish_main together for a list from any neighbour search (the unit of the
-//            nearest-return depths runs it; k_feature_trace keeps its own sequence of the same calls)
-//   host     DepthCalib / build_calib, inverse3, camera_to_lidar, window_halves, window_cells, window_span, and what
-//            mld_create refuses of a parameter set, a camera and a transform, with its texts (refuse_*)
+//            strings the last four and finish_main together for a list from any neighbour search: the ONE sequence of
+//            those calls among the batch units (k_feature_trace runs it behind its window scan, the unit of the
+//            nearest-return depths behind its nearest-first search); and the skeleton of a unit with one wavefront per
+//            feature: Lists, read_feature, store_record
+//   host     DepthCalib / build_calib, inverse3, camera_to_lidar, window_halves, window_cells, window_span, what
+//            mld_create refuses of a parameter set, a camera and a transform, with its texts (refuse_*), and what the
+//            collect calls of the per-feature units refuse alike (FeatureTables, feature_*_fault, feature_grid)
 // Every user is compiled without contraction.  The forms - values, references, a functor for what only one user stores -
 // are the ones that left the kernels' code objects alone (profiles/depth_path_header.md).
 #pragma once
@@ -60,8 +63,7 @@ __device__ __forceinline__ V3 vcross(V3 a, V3 b) {
     return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
 
-// Cyclic Jacobi eigen-decomposition of a symmetric 3x3 (s = xx, xy, xz, yy, yz, zz): the eigenvector of the smallest
-// eigenvalue.  Only the degenerate branch of plane_through comes here.
+// smallest_eigvec of mld_batch_device.h again: as one function k_sp_fit<0> moved 871 -> 769 instructions (profiles/feature_units.md)
 __device__ __forceinline__ V3 smallest_eigvec3(const double s[6]) {
     double a[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}};
     double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
@@ -529,6 +531,43 @@ __device__ __forceinline__ MainPath main_path(const DepthCalib& c, double u, dou
     return r;
 }
 
+// ---- the skeleton of a unit with one wavefront per feature and a grid of (sequence, feature)
+
+constexpr int kMaxGridY = 65535;  // features of a sequence beyond it share blocks (grid-stride)
+
+// The 32-bit lists of the feature a wavefront works on, beside its points (dynamic LDS; every kernel carves its own and a
+// unit extends them with what only it keeps).
+struct Lists : PointList {
+    int32_t* vis;  // visible index of list entry i
+    int32_t* aux;  // per entry, what a stage needs for a while: the original index the search leaves (of every entry, or in
+                   // [0] that of the first), then the histogram's bin (main_path's `bin`)
+    int32_t* pos;  // positions in the list of the points a stage keeps: the segmented points (main_path's keep(rank, i)),
+                   // in a road stage the plane's inliers
+};
+
+// Feature f of a sequence from its two tables: uv in f64 (v_tab unused), or the f32 u, v of the tracklet layer truncated to
+// the integer pixel it evaluates (std::pair<int,int>).
+template <bool kTracks>
+__device__ __forceinline__ void read_feature(const void* u_tab, const float* v_tab, int f, double& u, double& v) {
+    if (kTracks) {
+        u = (double)truncf(as_global(static_cast<const float*>(u_tab))[f]);
+        v = (double)truncf(as_global(v_tab)[f]);
+    } else {
+        u = as_global(static_cast<const double*>(u_tab))[2 * (size_t)f];
+        v = as_global(static_cast<const double*>(u_tab))[2 * (size_t)f + 1];
+    }
+}
+
+// The exit of a record lane 0 has staged in LDS: one store of a dword per lane.  Every lane is here (barriers); behind it
+// the next feature of the block may rewrite the lists and the staged record.
+template <typename Rec>
+__device__ __forceinline__ void store_record(const Rec* staged, Rec* out, int lane) {
+    static_assert(sizeof(Rec) % 4 == 0 && sizeof(Rec) / 4 <= kWave, "one dword per lane");
+    __syncthreads();
+    if (lane < (int)(sizeof(Rec) / 4)) as_global(reinterpret_cast<uint32_t*>(out))[lane] = reinterpret_cast<const uint32_t*>(staged)[lane];
+    __syncthreads();
+}
+
 // ---- the host side: the calibration and what is refused of it
 
 // 3x3 inverse by cofactors (Eigen compute_inverse<Matrix3d>): result(i,j) = cofactor<j,i> / det.
@@ -675,6 +714,73 @@ inline int refuse_wide_window_cells(const mld_params& P, const mld_camera& cam, 
         return MLD_ERR_CAPACITY;
     }
     return MLD_OK;
+}
+
+// What the collect calls of the per-feature units refuse alike of the feature tables (u = uv and v null, or kTracks: u, v)
+// and of the tables of the exported clouds, one entry per sequence each: every function returns the text of the first fault
+// or null.  In their order; a unit puts what only it refuses (its record table, its bounds, its lists) between and behind
+// them.  All are MLD_ERR_INVALID_ARG but feature_capacity_fault: MLD_ERR_CAPACITY.
+struct FeatureTables {
+    const void* const* u;
+    const float* const* v;
+    const int64_t* n_features;
+    const int32_t* const* map;
+    const int32_t* const* index;
+    const int64_t* index_len;
+    const double* const* cam;
+    const int64_t* n_points;
+};
+template <bool kTracks>
+inline const char* feature_table_fault(const FeatureTables& t) {
+    if (!t.u) return kTracks ? "null table u" : "null table uv";
+    if (kTracks && !t.v) return "null table v";
+    if (!t.n_features) return "null table n_features";
+    if (!t.map) return "null table map";
+    if (!t.index) return "null table index";
+    if (!t.index_len) return "null table index_len";
+    if (!t.cam) return "null table cam";
+    if (!t.n_points) return "null table n_points";
+    return nullptr;
+}
+// Sequence s: its counts,
+inline const char* feature_sign_fault(const FeatureTables& t, int s) {
+    if (t.n_features[s] < 0) return "negative n_features";
+    if (t.index_len[s] < 0) return "negative index_len";
+    if (t.n_points[s] < 0) return "negative n_points";
+    return nullptr;
+}
+inline const char* feature_capacity_fault(const FeatureTables& t, int s, int64_t max_features) {
+    if (t.n_features[s] > max_features) return "n_features exceeds the max_features of the object";
+    if (t.n_points[s] > kMaxPoints || t.index_len[s] > kMaxPoints) return "n_points or index_len exceeds 8 388 607";
+    return nullptr;
+}
+// and, when it has features, its arrays: there (a unit tests its record array behind these), then aligned.
+template <bool kTracks>
+inline const char* feature_array_fault(const FeatureTables& t, int s) {
+    if (!t.u[s]) return kTracks ? "null array u of a sequence with features" : "null array uv of a sequence with features";
+    if (kTracks && !t.v[s]) return "null array v of a sequence with features";
+    if (!t.map[s]) return "null array map of a sequence with features";
+    if (t.index_len[s] > 0 && !t.index[s]) return "null array index of a sequence with features and index_len > 0";
+    if (t.n_points[s] > 0 && !t.cam[s]) return "null array cam of a sequence with features and n_points > 0";
+    return nullptr;
+}
+template <bool kTracks>
+inline const char* feature_alignment_fault(const FeatureTables& t, int s) {
+    auto off = [](const void* p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (kTracks && off(t.u[s], 3u)) return "u must be 4-byte aligned";
+    if (kTracks && off(t.v[s], 3u)) return "v must be 4-byte aligned";
+    if (!kTracks && off(t.u[s], 7u)) return "uv must be 8-byte aligned";
+    if (off(t.map[s], 3u)) return "map must be 4-byte aligned";
+    if (off(t.index[s], 3u)) return "index must be 4-byte aligned";
+    if (off(t.cam[s], 7u)) return "cam must be 8-byte aligned";
+    return nullptr;
+}
+
+// The grid of a per-feature kernel for n_seq sequences, the longest of `longest` features; false: no feature, nothing to
+// launch.
+inline bool feature_grid(int n_seq, int64_t longest, dim3& grid) {
+    grid = dim3((unsigned)n_seq, (unsigned)(longest < kMaxGridY ? longest : kMaxGridY));
+    return longest > 0;
 }
 
 }  // namespace mld_batch

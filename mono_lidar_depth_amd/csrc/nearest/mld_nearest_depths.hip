@@ -36,8 +36,9 @@
 //
 // This translation unit uses the depth path through its public C-ABI only (mld_get_stream) and shares no internals with
 // it (descriptor ring and object skeleton: ../batch/mld_batch_object.h; as_global, V3, the wavefront helpers and the
-// size limits: ../batch/mld_batch_device.h; the main path, the calibration and the refusals it shares with mld_create:
-// ../batch/mld_depth_path.h).  It is compiled without contraction like the rest of the library; the records are bit for
+// size limits: ../batch/mld_batch_device.h; the main path, the calibration, the refusals it shares with mld_create, and
+// what it shares with the feature traces, the other unit of one wavefront per feature - the lists, the feature reader, the
+// record's exit, the common refusals of the collect calls, the grid: ../batch/mld_depth_path.h).  It is compiled without contraction like the rest of the library; the records are bit for
 // bit what the CPU restatement computes (tests/test_nearest_depths_gpu.py pins that).
 #include <hip/hip_runtime.h>
 
@@ -55,7 +56,6 @@ namespace {
 
 using namespace mld_batch;
 
-constexpr int kMaxGridY = 65535;  // features of a sequence beyond it share blocks (grid-stride)
 constexpr int kFirstStage = 4;    // half size of the first square
 constexpr int kInFlight = 4;     // steps of 64 cells whose loads a wavefront has in flight
 constexpr int kTieRoom = 32;      // cells that can share one d2 <= 4096 (1105 = 5 * 13 * 17 has 32 lattice points)
@@ -64,7 +64,6 @@ static_assert(sizeof(mld_nearest_depth) == 64, "64 bytes per record (include/mld
 static_assert(offsetof(mld_nearest_depth, depth) == 32 && offsetof(mld_nearest_depth, nearest_z) == 40 &&
                   offsetof(mld_nearest_depth, corner_vis) == 48 && alignof(mld_nearest_depth) == 8,
               "field offsets of the record (include/mld.h)");
-constexpr int kRecWords = (int)(sizeof(mld_nearest_depth) / 4);  // 16: one dword per lane
 static_assert(MLD_NEAREST_MAX_RADIUS == 64 && MLD_NEAREST_MAX_COUNT == 256, "the stages, the keys and the LDS budget assume them");
 
 // One sequence of one call.  Host-made, staged through the descriptor ring (mld_batch::DescRing).
@@ -83,11 +82,9 @@ struct NdSeq {
 };
 static_assert(sizeof(NdSeq) == 72, "72 bytes per sequence (include/mld.h, DESIGN.md)");
 
-// What a wavefront keeps of its feature (dynamic LDS).  k2 = k rounded up to even.
-struct Lists : PointList {       // x, y, z: k2 doubles each - the list's points, then the segmented ones in place
-    int32_t* vis;    // k2: visible index of list entry i
-    int32_t* aux;    // k2: [0] the original index of the first entry; then the histogram's bin of entry i
-    int32_t* pos;    // k2: positions of the segmented points in the list
+// What a wavefront keeps of its feature (dynamic LDS) beside the lists of the depth path's header (x, y, z, vis, aux, pos: k2
+// entries each, k2 = k rounded up to even; aux[0] is the original index of the first entry until the bins overwrite it).
+struct NearestLists : Lists {
     uint32_t* skey;  // k2: key of list entry i
     uint32_t* ckey;  // k + kTieRoom: keys of the gathered candidates, d2 << 16 | (dy + 64) << 8 | (dx + 64)
     int32_t* cm;     // their visible indices
@@ -123,9 +120,9 @@ __device__ __forceinline__ bool clip_square(const DepthCalib& c, int cx, int cy,
 
 // N1 to N3 for the centre cell (cx, cy): the list in L (points, vis, skey; aux[0]), its length; n_in: the candidates of the
 // whole disc.  Every lane is here.
-__device__ __forceinline__ int nearest_list(const DepthCalib& c, const NdSeq& q, const Lists& L, const int cx, const int cy, const int R,
-                                            const int K, const int lane, MLD_BATCH_GLOBAL int32_t* row, const int list_cap, int& n_in,
-                                            bool& bad) {
+__device__ __forceinline__ int nearest_list(const DepthCalib& c, const NdSeq& q, const NearestLists& L, const int cx, const int cy,
+                                            const int R, const int K, const int lane, MLD_BATCH_GLOBAL int32_t* row, const int list_cap,
+                                            int& n_in, bool& bad) {
     const MLD_BATCH_GLOBAL int32_t* map = as_global(q.map);
     const MLD_BATCH_GLOBAL int32_t* index = as_global(q.index);
     const MLD_BATCH_GLOBAL double* cam = as_global(q.cam);
@@ -275,16 +272,10 @@ __device__ __forceinline__ int nearest_list(const DepthCalib& c, const NdSeq& q,
 }
 
 template <bool kTracks>
-__device__ __forceinline__ void nearest_feature(const DepthCalib& c, const NdSeq& q, const Lists& L, mld_nearest_depth* rec, const int f,
-                                                const int lane, const int R, const int K, const int list_cap) {
+__device__ __forceinline__ void nearest_feature(const DepthCalib& c, const NdSeq& q, const NearestLists& L, mld_nearest_depth* rec,
+                                                const int f, const int lane, const int R, const int K, const int list_cap) {
     double u, v;
-    if (kTracks) {  // the integer pixel the tracklet layer evaluates (std::pair<int,int>)
-        u = (double)truncf(as_global(static_cast<const float*>(q.u))[f]);
-        v = (double)truncf(as_global(q.v)[f]);
-    } else {
-        u = as_global(static_cast<const double*>(q.u))[2 * (size_t)f];
-        v = as_global(static_cast<const double*>(q.u))[2 * (size_t)f + 1];
-    }
+    read_feature<kTracks>(q.u, q.v, f, u, v);
     const bool finite = isfinite(u) && isfinite(v);
     int flags = finite ? 0 : MLD_NEAREST_FLAG_NONFINITE_FEATURE;
     bool bad = false;
@@ -326,10 +317,7 @@ __device__ __forceinline__ void nearest_feature(const DepthCalib& c, const NdSeq
         rec->corner_vis[2] = mp.ci >= 0 ? L.vis[L.pos[mp.ck]] : -1;
         rec->pad_ = 0;
     }
-    __syncthreads();
-    if (lane < kRecWords)
-        as_global(reinterpret_cast<uint32_t*>(q.rec + f))[lane] = reinterpret_cast<const uint32_t*>(rec)[lane];
-    __syncthreads();  // (the next feature of this block rewrites the lists and the staged record)
+    store_record(rec, q.rec + f, lane);
 }
 
 // Bytes of dynamic LDS for count K and radius R, and the carving of them (the doubles first, the staged record behind
@@ -346,7 +334,7 @@ __global__ __launch_bounds__(kWave) void k_nearest_depths(const NdSeq* __restric
     const NdSeq q = desc[blockIdx.x];
     const int lane = (int)threadIdx.x;
     const int k2 = even_count(K), room = K + kTieRoom;
-    Lists L;
+    NearestLists L;
     L.x = reinterpret_cast<double*>(smem);
     L.y = L.x + k2;
     L.z = L.y + k2;
@@ -401,48 +389,26 @@ int collect(mld_nearest_depths* nd, const char* fn, const void* const* u_tab, co
             const int64_t* n_points, int list_capacity, mld_nearest_depth* const* record_out, int32_t* const* nb_out) {
     if (!nd) return no_object(g_error, fn, "nd");
     auto refuse = [&](int code, const char* text) { return fail(nd, code, (std::string(fn) + ": " + text).c_str()); };
-#define ND_REFUSE(text) return refuse(MLD_ERR_INVALID_ARG, text)
-    if (!u_tab) ND_REFUSE(kTracks ? "null table u" : "null table uv");
-    if (kTracks && !v_tab) ND_REFUSE("null table v");
-    if (!n_features) ND_REFUSE("null table n_features");
-    if (!map) ND_REFUSE("null table map");
-    if (!index) ND_REFUSE("null table index");
-    if (!index_len) ND_REFUSE("null table index_len");
-    if (!cam) ND_REFUSE("null table cam");
-    if (!n_points) ND_REFUSE("null table n_points");
-    if (!record_out) ND_REFUSE("null table record_out");
-    if (list_capacity < 0 || list_capacity > nd->count) ND_REFUSE("list_capacity must be in 0 .. count");
+    auto bad_arg = [&](const char* text) { return refuse(MLD_ERR_INVALID_ARG, text); };
+    const FeatureTables t = {u_tab, v_tab, n_features, map, index, index_len, cam, n_points};
+    const char* bad;
+    if ((bad = feature_table_fault<kTracks>(t))) return bad_arg(bad);
+    if (!record_out) return bad_arg("null table record_out");
+    if (list_capacity < 0 || list_capacity > nd->count) return bad_arg("list_capacity must be in 0 .. count");
     const int S = nd->n_seq;
     int64_t longest = 0;
     for (int s = 0; s < S; s++) {
+        if ((bad = feature_sign_fault(t, s))) return bad_arg(bad);
+        if ((bad = feature_capacity_fault(t, s, nd->max_features))) return refuse(MLD_ERR_CAPACITY, bad);
         const int64_t n = n_features[s];
-        if (n < 0) ND_REFUSE("negative n_features");
-        if (index_len[s] < 0) ND_REFUSE("negative index_len");
-        if (n_points[s] < 0) ND_REFUSE("negative n_points");
-        if (n > nd->max_features) return refuse(MLD_ERR_CAPACITY, "n_features exceeds the max_features of the object");
-        if (n_points[s] > kMaxPoints || index_len[s] > kMaxPoints)
-            return refuse(MLD_ERR_CAPACITY, "n_points or index_len exceeds 8 388 607");
         if (n == 0) continue;  // (needs no arrays)
-        if (!u_tab[s]) ND_REFUSE(kTracks ? "null array u of a sequence with features" : "null array uv of a sequence with features");
-        if (kTracks && !v_tab[s]) ND_REFUSE("null array v of a sequence with features");
-        if (!map[s]) ND_REFUSE("null array map of a sequence with features");
-        if (index_len[s] > 0 && !index[s]) ND_REFUSE("null array index of a sequence with features and index_len > 0");
-        if (n_points[s] > 0 && !cam[s]) ND_REFUSE("null array cam of a sequence with features and n_points > 0");
-        if (!record_out[s]) ND_REFUSE("null array record_out of a sequence with features");
-        if (kTracks) {
-            if (misaligned(u_tab[s], 3u)) ND_REFUSE("u must be 4-byte aligned");
-            if (misaligned(v_tab[s], 3u)) ND_REFUSE("v must be 4-byte aligned");
-        } else if (misaligned(u_tab[s], 7u)) {
-            ND_REFUSE("uv must be 8-byte aligned");
-        }
-        if (misaligned(map[s], 3u)) ND_REFUSE("map must be 4-byte aligned");
-        if (misaligned(index[s], 3u)) ND_REFUSE("index must be 4-byte aligned");
-        if (misaligned(cam[s], 7u)) ND_REFUSE("cam must be 8-byte aligned");
-        if (misaligned(record_out[s], 7u)) ND_REFUSE("record_out must be 8-byte aligned");
-        if (list_capacity > 0 && nb_out && misaligned(nb_out[s], 3u)) ND_REFUSE("nb_out must be 4-byte aligned");
+        if ((bad = feature_array_fault<kTracks>(t, s))) return bad_arg(bad);
+        if (!record_out[s]) return bad_arg("null array record_out of a sequence with features");
+        if ((bad = feature_alignment_fault<kTracks>(t, s))) return bad_arg(bad);
+        if (misaligned(record_out[s], 7u)) return bad_arg("record_out must be 8-byte aligned");
+        if (list_capacity > 0 && nb_out && misaligned(nb_out[s], 3u)) return bad_arg("nb_out must be 4-byte aligned");
         if (n > longest) longest = n;
     }
-#undef ND_REFUSE
     for (int s = 0; s < S; s++) {
         NdSeq& q = nd->ring.stage[(size_t)s];
         q = NdSeq{};
@@ -459,13 +425,13 @@ int collect(mld_nearest_depths* nd, const char* fn, const void* const* u_tab, co
         q.index_len = (int32_t)index_len[s];
         q.n_points = (int32_t)n_points[s];
     }
-    if (longest == 0) return MLD_OK;  // no feature, nothing to launch
+    dim3 grid;
+    if (!feature_grid(S, longest, grid)) return MLD_OK;
     MLD_HIP(nd, hipSetDevice(nd->device));
     const int rc = nd->ring.upload(nd);
     if (rc) return rc;
-    const unsigned gy = (unsigned)(longest < kMaxGridY ? longest : kMaxGridY);
-    hipLaunchKernelGGL(k_nearest_depths<kTracks>, dim3((unsigned)S, gy), dim3(kWave), nd->lds_bytes, nd->stream, nd->ring.d_desc.get(),
-                       nd->calib, nd->radius, nd->count, list_capacity);
+    hipLaunchKernelGGL(k_nearest_depths<kTracks>, grid, dim3(kWave), nd->lds_bytes, nd->stream, nd->ring.d_desc.get(), nd->calib,
+                       nd->radius, nd->count, list_capacity);
     MLD_HIP(nd, hipGetLastError());
     return MLD_OK;
 }

@@ -10,15 +10,15 @@
 //   k_feature_trace   grid (sequence, feature), ONE WAVEFRONT PER FEATURE, any window up to kMaxCells cells:
 //     B2  the lanes scan the window's cells in row-major order; ballot + prefix popcount give the ordered neighbour list
 //         in LDS (visible index, camera-frame point)                                   NeighborFinderPixel.cpp:60-95
-//     B3  the histogram's bins from ballots over the list, the scan for the first local maximum on the scalar side, the
-//         kept points compacted in place                                               HistogramPointDepth.cpp:15-123
-//     B5  the farthest pair: row i of the pair matrix spread over the lanes, every lane keeps (largest distance,
-//         smallest i * n + j), one (value descending, id ascending) reduction; the third corner likewise
-//                                                           PlaneEstimationCalcMaxSpanningTriangle.cpp:37-100
-//     B6  the serial tail - planarity, viewing ray, Hyperplane::Through, intersection, thresholds - on wave-uniform
-//         values; the record is staged in LDS by lane 0 and leaves as one store of a dword per lane
+//     B3 to B6  main_path of ../batch/mld_depth_path.h on that list: the count test; the histogram's bins from ballots
+//         over the list, the scan for the first local maximum on the scalar side, the kept points compacted in place
+//         (HistogramPointDepth.cpp:15-123); the farthest pair and the third corner by (value descending, id ascending)
+//         reductions (PlaneEstimationCalcMaxSpanningTriangle.cpp:37-100); the serial tail - planarity, viewing ray,
+//         Hyperplane::Through, intersection, thresholds - on wave-uniform values.  Its functor for the kept points also
+//         writes the seg row; lane 0 stages the corners' visible indices and the record's doubles in LDS at once
 //     road  the wide window as B2, then per neighbour the f32 point-to-plane distance after the f64 Tinv transform and the
-//         mask bit of its original index                                               DepthEstimator.cpp:782-900
+//         mask bit of its original index (DepthEstimator.cpp:782-900); then the record's integers, and the record leaves
+//         as one store of a dword per lane
 // The road fit itself is not repeated: its depth is the depth path's business.
 //
 // This translation unit uses the depth path through its public C-ABI only (mld_get_stream) and shares no internals with
@@ -26,10 +26,11 @@
 // size limits: ../batch/mld_batch_device.h).  The records are nevertheless bit for bit what that path and the CPU
 // restatement compute (tests/test_feature_traces_gpu.py pins that): the stages B2 to B6 are the functions of
 // ../batch/mld_depth_path.h, the batch units' one restatement, operation for operation, of that path's arithmetic
-// (gather_window, hist_segment, max_spanning_triangle, finish_main with plane_through, viewing_ray, intersect and the
-// thresholds, far_from_plane; Tinv and Kinv formed as mld_create forms them), and this unit is compiled without contraction
-// like the rest of the library.  What stands here is what only the trace has: the lists it keeps, the road states, the
-// record.
+// (gather_window, main_path, far_from_plane; Tinv and Kinv formed as mld_create forms them), and this unit is compiled
+// without contraction like the rest of the library.  That header also has what this unit shares with the other unit of one
+// wavefront per feature: the lists, the feature reader, the record's exit, the refusals of the collect calls they have in
+// common and the grid.  What stands here is what only the trace has: the rows it keeps, the road states, the record
+// (profiles/feature_units.md: what the move did to the kernel).
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -46,12 +47,9 @@ namespace {
 
 using namespace mld_batch;
 
-constexpr int kMaxGridY = 65535;       // features of a sequence beyond it share blocks (grid-stride)
-
 static_assert(sizeof(mld_feature_trace) == 184, "184 bytes per record (include/mld.h)");
 static_assert(offsetof(mld_feature_trace, main_depth) == 56 && offsetof(mld_feature_trace, corners) == 112,
               "field offsets of the record (include/mld.h)");
-constexpr int kRecWords = (int)(sizeof(mld_feature_trace) / 4);  // 46: one dword per lane
 
 // One sequence of one call.  Host-made, staged through the descriptor ring (mld_batch::DescRing).
 struct TrSeq {
@@ -74,13 +72,6 @@ struct TrSeq {
 };
 static_assert(sizeof(TrSeq) == 120, "120 bytes per sequence (include/mld.h, DESIGN.md)");
 
-// The lists of the feature a wavefront works on, c.cap entries each (dynamic LDS): the points (PointList::x, y, z) and
-struct Lists : PointList {
-    int32_t* vis;  // visible index of neighbour i
-    int32_t* aux;  // the histogram's bin of neighbour i; in the road stage its original index
-    int32_t* pos;  // positions of the segmented points in the neighbour list; in the road stage those of the inliers
-};
-
 // gather_window of the depth path's header; besides, the visible indices go into the list and into `row` (up to list_cap of
 // them), or row is null.
 __device__ __forceinline__ int gather_visible(const DepthCalib& c, const TrSeq& q, double u, double v, double halfX, double halfY,
@@ -96,72 +87,38 @@ template <bool kTracks>
 __device__ __forceinline__ void trace_feature(const DepthCalib& c, const TrSeq& q, const Lists& L, mld_feature_trace* rec,
                                               const int f, const int lane, const int list_cap) {
     double u, v;
-    if (kTracks) {  // the integer pixel the tracklet layer evaluates (std::pair<int,int>)
-        u = (double)truncf(as_global(static_cast<const float*>(q.u))[f]);
-        v = (double)truncf(as_global(q.v)[f]);
-    } else {
-        u = as_global(static_cast<const double*>(q.u))[2 * (size_t)f];
-        v = as_global(static_cast<const double*>(q.u))[2 * (size_t)f + 1];
-    }
+    read_feature<kTracks>(q.u, q.v, f, u, v);
     const size_t row = (size_t)f * (size_t)list_cap;
-    const double nan = __builtin_nan("");
     int flags = (isfinite(u) && isfinite(v)) ? 0 : MLD_TRACE_FLAG_NONFINITE_FEATURE;
     bool bad = false;
 
     // ---- B2: the narrow window (DepthEstimator.cpp:509, scale 1.0 x 1.0) ----
     const int n_nb = gather_visible(c, q, u, v, c.halfX1, c.halfY1, L, lane, q.nb ? as_global(q.nb) + row : nullptr, list_cap, bad);
     __syncthreads();
-    int main_type = MLD_Unspecified, n_seg = 0;
-    int cp0 = -1, cp1 = -1, cp2 = -1, cv0 = -1, cv1 = -1, cv2 = -1;
-    double main_depth = -1.0, lower = -1.0, higher = -1.0;
-    Plane pl = {{nan, nan, nan}, nan};
-    V3 c1 = {nan, nan, nan}, c2 = c1, c3 = c1;
-    if ((unsigned)n_nb < c.countMin) {  // :680, compared as unsigned
-        main_type = MLD_RadiusSearchInsufficientPoints;
-    } else {
-        // ---- B3: CalculateDepthSegmentation (:726-780) ----
-        int ks = n_nb;
-        if (c.useHist) {
-            ks = hist_segment(c, n_nb, L, L.aux, lane, lower, higher, [&](int rank, int i) { L.pos[rank] = i; });
-        } else {
-            for (int i = lane; i < n_nb; i += kWave) L.pos[i] = i;
-        }
-        __syncthreads();
-        if (ks < 0) {
-            main_type = MLD_HistogramNoLocalMax;
-        } else {
-            n_seg = ks;
-            if (q.seg) {
-                MLD_BATCH_GLOBAL int32_t* out = as_global(q.seg) + row;
-                const int m = ks < list_cap ? ks : list_cap;
-                for (int i = lane; i < m; i += kWave) out[i] = L.pos[i];
-            }
-            // ---- B5: the corners (:915-926) ----
-            bool ok = true;
-            int ci = 0, cj = 1, ck = 2;
-            if (c.useTriMax) {
-                ok = max_spanning_triangle(ks, L, lane, ci, cj, ck);
-                if (!ok) main_type = MLD_TriangleNotPlanarInsufficientPoints;
-            } else if (ks < 3) {
-                ok = false;
-                main_type = MLD_HistogramNoLocalMax;  // :920-921
-            }
-            if (ok) {
-                // ---- B6: the tail of CalculateDepthSegmented (:928-1036), on wave-uniform values ----
-                cp0 = ci, cp1 = cj, cp2 = ck;
-                cv0 = L.vis[L.pos[ci]], cv1 = L.vis[L.pos[cj]], cv2 = L.vis[L.pos[ck]];
-                c1 = list_point(L, ci), c2 = list_point(L, cj), c3 = list_point(L, ck);
-                double mn, mx;
-                list_minmax_z(ks, L, lane, mn, mx);
-                main_type = finish_main(c, u, v, c1, c2, c3, mn, mx, &pl, main_depth);
-            }
-        }
+    // ---- B3 to B6: the main path on the window's list ----
+    MLD_BATCH_GLOBAL int32_t* seg_row = q.seg ? as_global(q.seg) + row : nullptr;
+    const MainPath mp = main_path(c, u, v, n_nb, L, L.aux, lane, [&](int rank, int i) {
+        L.pos[rank] = i;
+        if (seg_row && rank < list_cap) seg_row[rank] = i;
+    });
+    int cv0 = -1, cv1 = -1, cv2 = -1;  // (one uniform branch: the six LDS reads of the corners are in flight together)
+    if (mp.ci >= 0) cv0 = L.vis[L.pos[mp.ci]], cv1 = L.vis[L.pos[mp.cj]], cv2 = L.vis[L.pos[mp.ck]];
+    if (lane == 0) {  // staged while the lists hold the corners: what was read from them, and the doubles (the registers go)
+        rec->corner_vis[0] = cv0, rec->corner_vis[1] = cv1, rec->corner_vis[2] = cv2;
+        rec->main_depth = mp.depth;
+        rec->hist_lower = mp.lower;
+        rec->hist_higher = mp.higher;
+        rec->plane_n[0] = mp.plane.n.x, rec->plane_n[1] = mp.plane.n.y, rec->plane_n[2] = mp.plane.n.z;
+        rec->plane_offset = mp.plane.offset;
+        rec->corners[0] = mp.c1.x, rec->corners[1] = mp.c1.y, rec->corners[2] = mp.c1.z;
+        rec->corners[3] = mp.c2.x, rec->corners[4] = mp.c2.y, rec->corners[5] = mp.c2.z;
+        rec->corners[6] = mp.c3.x, rec->corners[7] = mp.c3.y, rec->corners[8] = mp.c3.z;
     }
     __syncthreads();  // (the lists are rewritten from here)
 
     // ---- the road fallback (:578-597): the wide window, the distance test, the mask ----
     int road_state = MLD_TRACE_ROAD_NOT_REACHED, n_road = 0, n_inl = 0;
-    if (c.useRoad && q.mask && main_type != MLD_Success && main_type != MLD_RadiusSearchInsufficientPoints) {
+    if (c.useRoad && q.mask && mp.type != MLD_Success && mp.type != MLD_RadiusSearchInsufficientPoints) {
         n_road = gather_visible(c, q, u, v, c.halfX2, c.halfY2, L, lane, q.road ? as_global(q.road) + row : nullptr, list_cap, bad);
         __syncthreads();
         if ((unsigned)n_road < c.countMin) {  // :585-586
@@ -200,31 +157,19 @@ __device__ __forceinline__ void trace_feature(const DepthCalib& c, const TrSeq& 
     }
     if (bad) flags |= MLD_TRACE_FLAG_BAD_INPUT;
 
-    // ---- the record: staged by lane 0, stored as one dword per lane ----
+    // ---- the integers of the record; it leaves as one store of a dword per lane (profiles/feature_units.md: the forms) ----
     if (lane == 0) {
-        rec->main_type = main_type;
-        rec->road_state = road_state;
+        rec->main_type = mp.type;
         rec->n_nb = n_nb;
-        rec->n_seg = n_seg;
+        rec->n_seg = mp.n_seg;
+        rec->corner_pos[0] = mp.ci, rec->corner_pos[1] = mp.cj, rec->corner_pos[2] = mp.ck;
+        rec->road_state = road_state;
         rec->n_road = n_road;
         rec->n_road_inl = n_inl;
-        rec->corner_pos[0] = cp0, rec->corner_pos[1] = cp1, rec->corner_pos[2] = cp2;
-        rec->corner_vis[0] = cv0, rec->corner_vis[1] = cv1, rec->corner_vis[2] = cv2;
         rec->flags = flags;
         rec->pad_ = 0;
-        rec->main_depth = main_depth;
-        rec->hist_lower = lower;
-        rec->hist_higher = higher;
-        rec->plane_n[0] = pl.n.x, rec->plane_n[1] = pl.n.y, rec->plane_n[2] = pl.n.z;
-        rec->plane_offset = pl.offset;
-        rec->corners[0] = c1.x, rec->corners[1] = c1.y, rec->corners[2] = c1.z;
-        rec->corners[3] = c2.x, rec->corners[4] = c2.y, rec->corners[5] = c2.z;
-        rec->corners[6] = c3.x, rec->corners[7] = c3.y, rec->corners[8] = c3.z;
     }
-    __syncthreads();
-    if (lane < kRecWords)
-        as_global(reinterpret_cast<uint32_t*>(q.trace + f))[lane] = reinterpret_cast<const uint32_t*>(rec)[lane];
-    __syncthreads();  // (the next feature of this block rewrites the lists and the staged record)
+    store_record(rec, q.trace + f, lane);
 }
 
 // Grid (sequence, feature); one wavefront per block.  Dynamic LDS: the lists (36 bytes per entry of c.cap, an even number)
@@ -284,55 +229,33 @@ int collect(mld_feature_traces* ft, const char* fn, const void* const* u_tab, co
             int32_t* const* road_inl_out) {
     if (!ft) return no_object(g_error, fn, "ft");
     auto refuse = [&](int code, const char* text) { return fail(ft, code, (std::string(fn) + ": " + text).c_str()); };
-#define TR_REFUSE(text) return refuse(MLD_ERR_INVALID_ARG, text)
-    if (!u_tab) TR_REFUSE(kTracks ? "null table u" : "null table uv");
-    if (kTracks && !v_tab) TR_REFUSE("null table v");
-    if (!n_features) TR_REFUSE("null table n_features");
-    if (!map) TR_REFUSE("null table map");
-    if (!index) TR_REFUSE("null table index");
-    if (!index_len) TR_REFUSE("null table index_len");
-    if (!cam) TR_REFUSE("null table cam");
-    if (!n_points) TR_REFUSE("null table n_points");
-    if (!trace_out) TR_REFUSE("null table trace_out");
-    if (list_capacity < 0 || list_capacity > kMaxCells) TR_REFUSE("list_capacity must be in 0 .. 1024");
-    if ((coeffs != nullptr) != (mask_dev != nullptr)) TR_REFUSE("coeffs and mask_dev come together or not at all");
+    auto bad_arg = [&](const char* text) { return refuse(MLD_ERR_INVALID_ARG, text); };
+    const FeatureTables t = {u_tab, v_tab, n_features, map, index, index_len, cam, n_points};
+    const char* bad;
+    if ((bad = feature_table_fault<kTracks>(t))) return bad_arg(bad);
+    if (!trace_out) return bad_arg("null table trace_out");
+    if (list_capacity < 0 || list_capacity > kMaxCells) return bad_arg("list_capacity must be in 0 .. 1024");
+    if ((coeffs != nullptr) != (mask_dev != nullptr)) return bad_arg("coeffs and mask_dev come together or not at all");
     const int S = ft->n_seq;
     int64_t longest = 0;
     for (int s = 0; s < S; s++) {
+        if ((bad = feature_sign_fault(t, s))) return bad_arg(bad);
+        if ((bad = feature_capacity_fault(t, s, ft->max_features))) return refuse(MLD_ERR_CAPACITY, bad);
         const int64_t n = n_features[s];
-        if (n < 0) TR_REFUSE("negative n_features");
-        if (index_len[s] < 0) TR_REFUSE("negative index_len");
-        if (n_points[s] < 0) TR_REFUSE("negative n_points");
-        if (n > ft->max_features) return refuse(MLD_ERR_CAPACITY, "n_features exceeds the max_features of the object");
-        if (n_points[s] > kMaxPoints || index_len[s] > kMaxPoints)
-            return refuse(MLD_ERR_CAPACITY, "n_points or index_len exceeds 8 388 607");
         if (n == 0) continue;  // (needs no arrays)
-        if (!u_tab[s]) TR_REFUSE(kTracks ? "null array u of a sequence with features" : "null array uv of a sequence with features");
-        if (kTracks && !v_tab[s]) TR_REFUSE("null array v of a sequence with features");
-        if (!map[s]) TR_REFUSE("null array map of a sequence with features");
-        if (index_len[s] > 0 && !index[s]) TR_REFUSE("null array index of a sequence with features and index_len > 0");
-        if (n_points[s] > 0 && !cam[s]) TR_REFUSE("null array cam of a sequence with features and n_points > 0");
-        if (!trace_out[s]) TR_REFUSE("null array trace_out of a sequence with features");
-        if (kTracks) {
-            if (misaligned(u_tab[s], 3u)) TR_REFUSE("u must be 4-byte aligned");
-            if (misaligned(v_tab[s], 3u)) TR_REFUSE("v must be 4-byte aligned");
-        } else if (misaligned(u_tab[s], 7u)) {
-            TR_REFUSE("uv must be 8-byte aligned");
-        }
-        if (misaligned(map[s], 3u)) TR_REFUSE("map must be 4-byte aligned");
-        if (misaligned(index[s], 3u)) TR_REFUSE("index must be 4-byte aligned");
-        if (misaligned(cam[s], 7u)) TR_REFUSE("cam must be 8-byte aligned");
-        if (mask_dev && misaligned(mask_dev[s], 3u)) TR_REFUSE("mask_dev must be 4-byte aligned");
-        if (misaligned(trace_out[s], 7u)) TR_REFUSE("trace_out must be 8-byte aligned");
+        if ((bad = feature_array_fault<kTracks>(t, s))) return bad_arg(bad);
+        if (!trace_out[s]) return bad_arg("null array trace_out of a sequence with features");
+        if ((bad = feature_alignment_fault<kTracks>(t, s))) return bad_arg(bad);
+        if (mask_dev && misaligned(mask_dev[s], 3u)) return bad_arg("mask_dev must be 4-byte aligned");
+        if (misaligned(trace_out[s], 7u)) return bad_arg("trace_out must be 8-byte aligned");
         if (list_capacity > 0) {
-            if (nb_out && misaligned(nb_out[s], 3u)) TR_REFUSE("nb_out must be 4-byte aligned");
-            if (seg_out && misaligned(seg_out[s], 3u)) TR_REFUSE("seg_out must be 4-byte aligned");
-            if (road_out && misaligned(road_out[s], 3u)) TR_REFUSE("road_out must be 4-byte aligned");
-            if (road_inl_out && misaligned(road_inl_out[s], 3u)) TR_REFUSE("road_inl_out must be 4-byte aligned");
+            if (nb_out && misaligned(nb_out[s], 3u)) return bad_arg("nb_out must be 4-byte aligned");
+            if (seg_out && misaligned(seg_out[s], 3u)) return bad_arg("seg_out must be 4-byte aligned");
+            if (road_out && misaligned(road_out[s], 3u)) return bad_arg("road_out must be 4-byte aligned");
+            if (road_inl_out && misaligned(road_inl_out[s], 3u)) return bad_arg("road_inl_out must be 4-byte aligned");
         }
         if (n > longest) longest = n;
     }
-#undef TR_REFUSE
     for (int s = 0; s < S; s++) {
         TrSeq& q = ft->ring.stage[(size_t)s];
         q = TrSeq{};
@@ -355,13 +278,13 @@ int collect(mld_feature_traces* ft, const char* fn, const void* const* u_tab, co
         q.index_len = (int32_t)index_len[s];
         q.n_points = (int32_t)n_points[s];
     }
-    if (longest == 0) return MLD_OK;  // nothing to trace, nothing to launch
+    dim3 grid;
+    if (!feature_grid(S, longest, grid)) return MLD_OK;
     MLD_HIP(ft, hipSetDevice(ft->device));
     const int rc = ft->ring.upload(ft);
     if (rc) return rc;
-    const unsigned gy = (unsigned)(longest < kMaxGridY ? longest : kMaxGridY);
-    hipLaunchKernelGGL(k_feature_trace<kTracks>, dim3((unsigned)S, gy), dim3(kWave), ft->lds_bytes, ft->stream, ft->ring.d_desc.get(),
-                       ft->calib, list_capacity);
+    hipLaunchKernelGGL(k_feature_trace<kTracks>, grid, dim3(kWave), ft->lds_bytes, ft->stream, ft->ring.d_desc.get(), ft->calib,
+                       list_capacity);
     MLD_HIP(ft, hipGetLastError());
     return MLD_OK;
 }

@@ -779,7 +779,60 @@ class PlaneInliers(_BatchObject):
         self._hold(clouds, masks, counts, index, lidar, cam)
 
 
-class FeatureTraces(_BatchObject):
+class _FeatureUnit(_BatchObject):
+    """What FeatureTraces and NearestDepths share - one record per feature, on the tensors ProjectedClouds.export wrote:
+    the feature tables of both forms with their refusals, what the exported cloud of a sequence with features must hold,
+    the leading arguments of the C calls, and records().  WORDS: int64 words of a record, DTYPE: its fields."""
+
+    @classmethod
+    def records(cls, record) -> np.ndarray:
+        """A record tensor (int64 [n, WORDS]) as a NumPy record array with the fields of DTYPE (copies to the host,
+        which synchronises as usual)."""
+        return np.ascontiguousarray(record.cpu().numpy()).reshape(-1).view(cls.DTYPE)
+
+    def _uv_counts(self, uv):
+        """The features of every sequence from the float64 table uv."""
+        self._lengths(uv=uv)
+        for s, t in enumerate(uv):
+            _holds(t, s, 0, 8, "uv")
+            if _entries(t) % 2:
+                raise ValueError(f"sequence {s}: uv must be a contiguous float64 tensor [n, 2]")
+        return [_entries(t, 2) for t in uv]
+
+    def _track_counts(self, u, v):
+        """The features of every sequence from the float32 tables u, v of the tracklet layer."""
+        self._lengths(u=u, v=v)
+        for s, (a, b) in enumerate(zip(u, v)):
+            if (a is None) != (b is None):
+                raise ValueError(f"sequence {s}: u and v come together")
+            _holds(a, s, 0, 4, "u")
+            _holds(b, s, 0, 4, "v")
+            if _entries(b) != _entries(a):
+                raise ValueError(f"sequence {s}: u and v must be contiguous float32 tensors of one length")
+        return [_entries(a) for a in u]
+
+    def _cloud_holds(self, ns, maps, index, cam, name, record, cap, lists):
+        """The exported cloud of a sequence with features holds what it must, its record tensor `name` and, with a
+        capacity, its rows of `lists` (name: table) as well."""
+        for s, n in enumerate(ns):
+            if n == 0:  # (nothing of a sequence without features is looked at)
+                continue
+            _holds(maps[s], s, self.width * self.height, 4, "pixel_map", required=True)
+            _holds(index[s], s, 0, 4, "index")
+            _holds(cam[s], s, 0, 8, "cam")
+            _holds(record[s], s, self.WORDS * n, 8, name, required=True)
+            for row, ts in lists.items():
+                if cap:
+                    _holds(_at(ts, s), s, cap * n, 4, row)
+
+    def _cloud_args(self, ns, feats, maps, index, cam):
+        """What both C calls of both units begin with behind the object: the feature tables, the counts, the cloud."""
+        vp = self._ptrs
+        return (*[vp(t) for t in feats], self._i64(ns), vp(maps), vp(index), self._i64(_entries(t) for t in index), vp(cam),
+                self._i64(_entries(t, 3) for t in cam))
+
+
+class FeatureTraces(_FeatureUnit):
     """Why a feature got the depth it got, for S sequences per call (mld_feature_traces_*, include/mld.h): per feature
     the record the reference calls DepthCalcStatsSinglePoint - neighbour and segmented counts, histogram borders, corner
     positions, the plane - with the triangle corners of getCloudTriangleCorners and the state the road fallback ended in,
@@ -799,34 +852,18 @@ class FeatureTraces(_BatchObject):
         self._create(estimator, self.S, self.max_features,
                      *self._calibration(estimator, "parameters", "camera", "transform", parameters=parameters))
 
-    @classmethod
-    def records(cls, trace) -> np.ndarray:
-        """A trace tensor (int64 [n, 23]) as a NumPy record array with the fields of capi.MldFeatureTrace (copies to
-        the host, which synchronises as usual)."""
-        return np.ascontiguousarray(trace.cpu().numpy()).reshape(-1).view(cls.DTYPE)
-
     def _collect(self, ns, feats, maps, index, cam, trace, coeffs, masks, list_capacity, lists):
         cap = int(list_capacity)
-        names = ("nb", "seg", "road", "road_inl")
-        self._lengths(pixel_map=maps, index=index, cam=cam, trace=trace, masks=masks, **dict(zip(names, lists)))
+        lists = dict(zip(("nb", "seg", "road", "road_inl"), lists))
+        self._lengths(pixel_map=maps, index=index, cam=cam, trace=trace, masks=masks, **lists)
         if not 0 <= cap <= self.MAX_LIST:
             raise ValueError(f"list_capacity must be in 0 .. {self.MAX_LIST}")
         planes = self._plane_args(coeffs, masks)
-        for s, n in enumerate(ns):
-            if n == 0:  # (nothing of a sequence without features is looked at)
-                continue
-            _holds(maps[s], s, self.width * self.height, 4, "pixel_map", required=True)
-            _holds(index[s], s, 0, 4, "index")
-            _holds(cam[s], s, 0, 8, "cam")
-            _holds(trace[s], s, self.WORDS * n, 8, "trace", required=True)
-            for name, ts in zip(names, lists):
-                if cap:
-                    _holds(_at(ts, s), s, cap * n, 4, name)
-        vp = self._ptrs
+        self._cloud_holds(ns, maps, index, cam, "trace", trace, cap, lists)
         fn = self._lib.mld_feature_traces_collect_device if len(feats) == 1 else self._lib.mld_feature_traces_collect_tracks_device
-        self._check(fn(self._ft, *[vp(t) for t in feats], self._i64(ns), vp(maps), vp(index), self._i64(_entries(t) for t in index),
-                       vp(cam), self._i64(_entries(t, 3) for t in cam), *planes, cap, vp(trace), *[self._opt(ts) for ts in lists]))
-        self._hold(*feats, maps, index, cam, trace, masks, *lists)
+        self._check(fn(self._ft, *self._cloud_args(ns, feats, maps, index, cam), *planes, cap, self._ptrs(trace),
+                       *[self._opt(ts) for ts in lists.values()]))
+        self._hold(*feats, maps, index, cam, trace, masks, *lists.values())
 
     def collect(self, uv, pixel_map, index, cam, trace, coeffs=None, masks=None, list_capacity: int = 0, nb=None, seg=None,
                 road=None, road_inl=None):
@@ -837,27 +874,14 @@ class FeatureTraces(_BatchObject):
         tensors, an entry None: that sequence has no plane): both or neither; nb, seg, road, road_inl: None, or S int32
         CUDA tensors of at least list_capacity * n entries (a contiguous [n, list_capacity]; single entries may be None).
         A row receives the first min(count, list_capacity) entries of its list; the counts of the record are complete."""
-        self._lengths(uv=uv)
-        for s, t in enumerate(uv):
-            _holds(t, s, 0, 8, "uv")
-            if _entries(t) % 2:
-                raise ValueError(f"sequence {s}: uv must be a contiguous float64 tensor [n, 2]")
-        self._collect([_entries(t, 2) for t in uv], (uv,), pixel_map, index, cam, trace, coeffs, masks, list_capacity,
+        self._collect(self._uv_counts(uv), (uv,), pixel_map, index, cam, trace, coeffs, masks, list_capacity,
                       (nb, seg, road, road_inl))
 
     def collect_tracks(self, u, v, pixel_map, index, cam, trace, coeffs=None, masks=None, list_capacity: int = 0, nb=None,
                        seg=None, road=None, road_inl=None):
         """As collect(), on the tensors of TrackletBatch.prepare_step() / prepare(): u, v (u_new, v_new): S float32 CUDA
         tensors [n]."""
-        self._lengths(u=u, v=v)
-        for s, (a, b) in enumerate(zip(u, v)):
-            if (a is None) != (b is None):
-                raise ValueError(f"sequence {s}: u and v come together")
-            _holds(a, s, 0, 4, "u")
-            _holds(b, s, 0, 4, "v")
-            if _entries(b) != _entries(a):
-                raise ValueError(f"sequence {s}: u and v must be contiguous float32 tensors of one length")
-        self._collect([_entries(a) for a in u], (u, v), pixel_map, index, cam, trace, coeffs, masks, list_capacity,
+        self._collect(self._track_counts(u, v), (u, v), pixel_map, index, cam, trace, coeffs, masks, list_capacity,
                       (nb, seg, road, road_inl))
 
 
@@ -1042,7 +1066,7 @@ class RegionDepths(_BatchObject):
         self._hold(pixel_map, index, cam, boxes, record, masks)
 
 
-class NearestDepths(_BatchObject):
+class NearestDepths(_FeatureUnit):
     """The main path on the `count` closest returns of a feature within `radius` pixels, for S sequences per call
     (mld_nearest_depths_*, include/mld.h): an exact nearest-first search over the cells of the pixel map - ascending
     (squared pixel distance, y, x) - in place of the fixed pixelarea_search rectangle, so that the list follows the local
@@ -1064,30 +1088,14 @@ class NearestDepths(_BatchObject):
         self._create(estimator, self.S, self.max_features, self.radius, self.count,
                      *self._calibration(estimator, "parameters", "camera", parameters=parameters))
 
-    @classmethod
-    def records(cls, record) -> np.ndarray:
-        """A record tensor (int64 [n, 8]) as a NumPy record array with the fields of capi.MldNearestDepth (copies to
-        the host, which synchronises as usual)."""
-        return np.ascontiguousarray(record.cpu().numpy()).reshape(-1).view(cls.DTYPE)
-
     def _collect(self, ns, feats, maps, index, cam, record, list_capacity, nb):
         cap = int(list_capacity)
         self._lengths(pixel_map=maps, index=index, cam=cam, record=record, nb=nb)
         if not 0 <= cap <= self.count:
             raise ValueError(f"list_capacity must be in 0 .. {self.count}")
-        for s, n in enumerate(ns):
-            if n == 0:  # (nothing of a sequence without features is looked at)
-                continue
-            _holds(maps[s], s, self.width * self.height, 4, "pixel_map", required=True)
-            _holds(index[s], s, 0, 4, "index")
-            _holds(cam[s], s, 0, 8, "cam")
-            _holds(record[s], s, self.WORDS * n, 8, "record", required=True)
-            if cap:
-                _holds(_at(nb, s), s, cap * n, 4, "nb")
-        vp = self._ptrs
+        self._cloud_holds(ns, maps, index, cam, "record", record, cap, {"nb": nb})
         fn = self._lib.mld_nearest_depths_collect_device if len(feats) == 1 else self._lib.mld_nearest_depths_collect_tracks_device
-        self._check(fn(self._nd, *[vp(t) for t in feats], self._i64(ns), vp(maps), vp(index), self._i64(_entries(t) for t in index),
-                       vp(cam), self._i64(_entries(t, 3) for t in cam), cap, vp(record), self._opt(nb)))
+        self._check(fn(self._nd, *self._cloud_args(ns, feats, maps, index, cam), cap, self._ptrs(record), self._opt(nb)))
         self._hold(*feats, maps, index, cam, record, nb)
 
     def collect(self, uv, pixel_map, index, cam, record, list_capacity: int = 0, nb=None):
@@ -1098,25 +1106,12 @@ class NearestDepths(_BatchObject):
         list_capacity * n entries (a contiguous [n, list_capacity]; single entries may be None): the visible indices of
         the list, nearest first.  A row receives the first min(n_nb, list_capacity) entries; list_capacity is at most
         `count`."""
-        self._lengths(uv=uv)
-        for s, t in enumerate(uv):
-            _holds(t, s, 0, 8, "uv")
-            if _entries(t) % 2:
-                raise ValueError(f"sequence {s}: uv must be a contiguous float64 tensor [n, 2]")
-        self._collect([_entries(t, 2) for t in uv], (uv,), pixel_map, index, cam, record, list_capacity, nb)
+        self._collect(self._uv_counts(uv), (uv,), pixel_map, index, cam, record, list_capacity, nb)
 
     def collect_tracks(self, u, v, pixel_map, index, cam, record, list_capacity: int = 0, nb=None):
         """As collect(), on the tensors of TrackletBatch.prepare_step() / prepare(): u, v (u_new, v_new): S float32 CUDA
         tensors [n]."""
-        self._lengths(u=u, v=v)
-        for s, (a, b) in enumerate(zip(u, v)):
-            if (a is None) != (b is None):
-                raise ValueError(f"sequence {s}: u and v come together")
-            _holds(a, s, 0, 4, "u")
-            _holds(b, s, 0, 4, "v")
-            if _entries(b) != _entries(a):
-                raise ValueError(f"sequence {s}: u and v must be contiguous float32 tensors of one length")
-        self._collect([_entries(a) for a in u], (u, v), pixel_map, index, cam, record, list_capacity, nb)
+        self._collect(self._track_counts(u, v), (u, v), pixel_map, index, cam, record, list_capacity, nb)
 
 
 class SweepMerge(_BatchObject):
@@ -1463,6 +1458,17 @@ class TrackletBatch:
         takes the estimator's parameters as they are now."""
         return self._attach("feature_traces")
 
+    def _feature_tables(self, f, clouds):
+        """The opening of traces() and nearest_depths(): `clouds` holds what the units read; the u_new, v_new of table
+        `f`, whose writers the call will wait for, their device and the tracks of every sequence."""
+        import torch
+        if clouds.get("cam") is None or clouds.get("pixel_map") is None:
+            raise ValueError("clouds: projected_clouds(cam=True, pixel_map=True) of this frame")
+        u_new, v_new = f["features"]
+        dev = next((t.device for t in u_new if t is not None), torch.device("cuda", self.est._device))
+        self.est._after_torch(*[t for t in u_new if t is not None][:1])
+        return u_new, v_new, dev, [_entries(t) for t in u_new]
+
     def traces(self, f, clouds, list_capacity: int = 0, planes: bool = True):
         """Why the tracks of table `f` (prepare_step() / prepare()) got their depths on this frame's clouds:
         FeatureTraces.collect_tracks on the table's u_new, v_new, its planes and masks (planes=False: traced without a
@@ -1474,17 +1480,12 @@ class TrackletBatch:
         attach_traces() first."""
         import torch
         traces = self._attached("feature_traces", "traces")
-        if clouds.get("cam") is None or clouds.get("pixel_map") is None:
-            raise ValueError("clouds: projected_clouds(cam=True, pixel_map=True) of this frame")
-        u_new, v_new = f["features"]
-        dev = next((t.device for t in u_new if t is not None), torch.device("cuda", self.est._device))
-        ns = [_entries(t) for t in u_new]
+        u_new, v_new, dev, ns = self._feature_tables(f, clouds)
         cap = int(list_capacity)
         names = ("nb", "seg", "road", "road_inl")
         out = {"trace": [torch.empty((n, FeatureTraces.WORDS), dtype=torch.int64, device=dev) for n in ns]}
         for name in names:
             out[name] = [torch.empty((n, cap), dtype=torch.int32, device=dev) for n in ns] if cap else None
-        self.est._after_torch(*[t for t in u_new if t is not None][:1])
         traces.collect_tracks(u_new, v_new, clouds["pixel_map"], clouds["index"], clouds["cam"], out["trace"],
                               f["coeffs"] if planes else None, list(f["keep"][1]) if planes else None, cap,
                               *[out[name] for name in names])
@@ -1599,15 +1600,10 @@ class TrackletBatch:
         current stream is made to wait for the call; a host read synchronises as usual.  attach_nearest_depths() first."""
         import torch
         nd = self._attached("nearest_depth_lists", "nearest_depths")
-        if clouds.get("cam") is None or clouds.get("pixel_map") is None:
-            raise ValueError("clouds: projected_clouds(cam=True, pixel_map=True) of this frame")
-        u_new, v_new = f["features"]
-        dev = next((t.device for t in u_new if t is not None), torch.device("cuda", self.est._device))
-        ns = [_entries(t) for t in u_new]
+        u_new, v_new, dev, ns = self._feature_tables(f, clouds)
         cap = int(list_capacity)
         out = {"record": [torch.empty((n, NearestDepths.WORDS), dtype=torch.int64, device=dev) for n in ns],
                "nb": [torch.empty((n, cap), dtype=torch.int32, device=dev) for n in ns] if cap else None}
-        self.est._after_torch(*[t for t in u_new if t is not None][:1])
         nd.collect_tracks(u_new, v_new, clouds["pixel_map"], clouds["index"], clouds["cam"], out["record"], cap, out["nb"])
         self.est.orderTorchAfter()
         return out

@@ -60,7 +60,9 @@ def test_the_functions_of_the_depth_path_header_exist_once_among_the_batch_units
     names = ("prefix_count", "uniform", "reduce_best", "wave_sum", "wave_max", "vsub", "vadd", "vscale", "vdivs", "vdot", "vsqnorm",
              "vnorm", "vnormalized", "vcross", "smallest_eigvec3", "plane_through", "viewing_ray", "intersect", "apply_thresholds",
              "finish_main", "window_bounds", "far_from_plane", "mask_bit", "list_point", "max_spanning_triangle", "list_minmax_z",
-             "hist_segment", "gather_window", "inverse3", "window_cells", "window_span", "build_calib")
+             "hist_segment", "gather_window", "inverse3", "window_cells", "window_span", "build_calib", "main_path", "read_feature",
+             "store_record", "feature_table_fault", "feature_sign_fault", "feature_capacity_fault", "feature_array_fault",
+             "feature_alignment_fault", "feature_grid")
     shared = {"mld_batch_device.h", "mld_depth_path.h"}
     for path in CSRC.rglob("*"):
         if not path.is_file() or path.parent == CSRC:
@@ -82,3 +84,12 @@ def test_the_functions_of_the_depth_path_header_exist_once_among_the_batch_units
     for name in names:
         n = len(re.findall(r"^(?:template[^\n]*\n)?[\w \t:<>&*]*[\w>&*]\s+" + name + r"\([^;{]*\)\s*\{", both, flags=re.M))
         assert n == (2 if name in ("wave_sum", "mask_bit") else 1), (name, n)
+
+
+def test_the_feature_traces_run_the_main_path_of_the_header():
+    """The sequence of calls behind the neighbour search exists once among the batch units: the trace names main_path and
+    none of the functions it strings together."""
+    code = re.sub(r"//.*", "", (CSRC / "traces" / "mld_feature_traces.hip").read_text())
+    assert "main_path(" in code
+    for name in ("hist_segment(", "max_spanning_triangle(", "list_minmax_z(", "finish_main("):
+        assert name not in code, name

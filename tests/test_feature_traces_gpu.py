@@ -516,6 +516,36 @@ def test_three_collinear_neighbours_take_the_degenerate_plane_like_the_depth_cal
         est.close()
 
 
+@pytest.mark.parametrize("tracks", [False, True])
+def test_the_exits_of_the_main_path_without_histogram_and_triangle_maximisation(tracks):
+    """16 x 16, one sequence, histogram segmentation and triangle maximisation off, radiusSearch_count_min 2, a 2 x 2 search
+    area (windows of 3 x 3 cells).  A window of two returns leaves at DepthEstimator.cpp:920-921 - the type of a failed
+    histogram, but n_seg 2 and its seg row written; a window of three takes the corners (0, 1, 2); windows of one return and
+    of none fail the count test.  With a plane, so the road stage follows the exit.  Records and rows equal the
+    restatement, between guard words."""
+    P = C0.replace(do_use_histogram_segmentation=0, do_use_triangle_size_maximation=0, radiusSearch_count_min=2,
+                   pixelarea_search_witdh=2, pixelarea_search_height=2)
+    cam = CameraPinhole(*R.COLLINEAR_CAM)
+    pixels = np.array([(2, 2), (3, 2), (9, 2), (10, 2), (10, 3), (3, 10)], dtype=np.float64)
+    z = np.array([10.0, 10.25, 10.0, 10.125, 10.25, 10.0])
+    cl = np.zeros((6, 4), dtype=np.float32)
+    cl[:, 0], cl[:, 1], cl[:, 2] = (pixels[:, 0] + 0.5 - 8.0) / 16.0 * z, (pixels[:, 1] + 0.5 - 8.0) / 16.0 * z, z
+    plane = (np.array([0.0, 0.0, 1.0, -10.125], dtype=np.float32), np.arange(6, dtype=np.int32))
+    uv = np.array([(2, 2), (10, 2), (3, 10), (12, 12)], dtype=np.float64)
+    fr = R.Restatement(P, cl, plane, cam, SMALL_T)
+    rec, lists, _ = fr.trace(uv)
+    assert rec["n_nb"].tolist() == [2, 3, 1, 0] and rec["n_seg"].tolist() == [2, 3, 0, 0]
+    assert rec["main_type"][[0, 2, 3]].tolist() == [3, 2, 2] and rec["corner_pos"].tolist() == [[-1] * 3, [0, 1, 2], [-1] * 3, [-1] * 3]
+    assert lists[0]["seg"].tolist() == [0, 1] and rec["road_state"][0] != R.NOT_REACHED
+    est = make_estimator(P, camera=cam, T=SMALL_T, max_frames=1)
+    try:
+        ft = FeatureTraces(est, 1, 4)
+        check(run(ft, prepare([fr], [uv], 4, tracks=tracks))[0], rec, lists, 4, tracks)
+        ft.close()
+    finally:
+        est.close()
+
+
 def test_tracklet_batch_traces_runs_on_the_exported_clouds(hdl64):
     """TrackletBatch.traces on the products of projected_clouds(cam=True, pixel_map=True) and the planes of the frame
     table: the records of the integer-pixel features equal the restatement."""

@@ -553,3 +553,83 @@ def test_close_destroys_the_object_before_the_estimator(monkeypatch):
     assert order == ["nearest_depths", "estimator"] and tb.nearest_depth_lists is None and nd._nd is None
     torch.cuda.synchronize()
     check(read(d)[0], expected(q, uv, 10, 16), "the call queued ahead of close()")
+
+
+def _tables():
+    import ctypes as C
+    tab, zero = (C.c_void_p * 1)(None), (C.c_int64 * 1)(0)
+    return dict(uv=tab, v=tab, n=zero, map=tab, index=tab, index_len=zero, cam=tab, n_points=zero, cap=0, record=tab, nb=None)
+
+
+def _refusals():
+    """(what differs from _tables(), status, word, forms: "both", or the one form the word belongs to)"""
+    import ctypes as C
+    INV, CAP = capi.MLD_ERR_INVALID_ARG, capi.MLD_ERR_CAPACITY
+    i64, ptr = (lambda v: (C.c_int64 * 1)(v)), (lambda v: (C.c_void_p * 1)(v))
+    one = i64(1)
+    there = dict(n=one, uv=ptr(0x1000), v=ptr(0x1000), map=ptr(0x1000), record=ptr(0x1000))  # (made-up addresses: never touched)
+    return [
+        (dict(uv=None), INV, "null table uv", "uv"),
+        (dict(uv=None), INV, "null table u", "tracks"),
+        (dict(v=None), INV, "null table v", "tracks"),
+        (dict(n=None), INV, "null table n_features", "both"),
+        (dict(map=None), INV, "null table map", "both"),
+        (dict(index=None), INV, "null table index", "both"),
+        (dict(index_len=None), INV, "null table index_len", "both"),
+        (dict(cam=None), INV, "null table cam", "both"),
+        (dict(n_points=None), INV, "null table n_points", "both"),
+        (dict(record=None), INV, "null table record_out", "both"),
+        (dict(cap=-1), INV, "list_capacity must be in 0 .. count", "both"),
+        (dict(cap=17), INV, "list_capacity must be in 0 .. count", "both"),
+        (dict(n=i64(-1)), INV, "negative n_features", "both"),
+        (dict(index_len=i64(-1)), INV, "negative index_len", "both"),
+        (dict(n_points=i64(-1)), INV, "negative n_points", "both"),
+        (dict(n=i64(601)), CAP, "n_features exceeds the max_features", "both"),
+        (dict(n_points=i64(8388608)), CAP, "8 388 607", "both"),
+        (dict(index_len=i64(8388608)), CAP, "8 388 607", "both"),
+        (dict(there, uv=ptr(None)), INV, "null array uv", "uv"),
+        (dict(there, uv=ptr(None)), INV, "null array u of", "tracks"),
+        (dict(there, v=ptr(None)), INV, "null array v of", "tracks"),
+        (dict(there, map=ptr(None)), INV, "null array map", "both"),
+        (dict(there, record=ptr(None)), INV, "null array record_out", "both"),
+        (dict(there, index_len=one), INV, "null array index", "both"),
+        (dict(there, n_points=one), INV, "null array cam", "both"),
+        (dict(there, uv=ptr(0x1004)), INV, "uv must be 8-byte aligned", "uv"),
+        (dict(there, uv=ptr(0x1002)), INV, "u must be 4-byte aligned", "tracks"),
+        (dict(there, v=ptr(0x1002)), INV, "v must be 4-byte aligned", "tracks"),
+        (dict(there, map=ptr(0x1002)), INV, "map must be 4-byte aligned", "both"),
+        (dict(there, index=ptr(0x1002)), INV, "index must be 4-byte aligned", "both"),
+        (dict(there, cam=ptr(0x1004)), INV, "cam must be 8-byte aligned", "both"),
+        (dict(there, record=ptr(0x1004)), INV, "record_out must be 8-byte aligned", "both"),
+        (dict(there, cap=4, nb=ptr(0x1002)), INV, "nb_out must be 4-byte aligned", "both"),
+    ]
+
+
+def test_collect_refuses_with_a_text_that_names_the_function_and_the_argument():
+    """Every refusal of both collect calls, decided on the host before anything is queued: none of the made-up addresses
+    is touched and no kernel runs.  A call with one fault reports it with its status, behind the function's name; where the
+    word does not belong to one form of the features, both forms are asked.  At the end a call on good tables is accepted."""
+    est = make_estimator(C0, camera=F.camera(16, 16), T=F.SMALL_T, max_frames=1)
+    nd = NearestDepths(est, 1, 600, 10, 16)
+    lib = capi.load()
+    try:
+        def both(a):
+            tail = (a["n"], a["map"], a["index"], a["index_len"], a["cam"], a["n_points"], a["cap"], a["record"], a["nb"])
+            return {"uv": ("mld_nearest_depths_collect_device", lib.mld_nearest_depths_collect_device, (a["uv"],) + tail),
+                    "tracks": ("mld_nearest_depths_collect_tracks_device", lib.mld_nearest_depths_collect_tracks_device,
+                               (a["uv"], a["v"]) + tail)}
+
+        asked = 0
+        for bad, code, word, forms in _refusals():
+            for form, (name, fn, args) in both(dict(_tables(), **bad)).items():
+                if forms in ("both", form):
+                    rc = fn(nd._nd, *args)
+                    text = lib.mld_nearest_depths_last_error(nd._nd).decode()
+                    assert rc == code and text.startswith(name + ": ") and word in text, (bad.keys(), form, rc, text)
+                    asked += 1
+        assert asked == 24 * 2 + 3 + 6
+        for name, fn, args in both(_tables()).values():
+            assert fn(nd._nd, *args) == capi.MLD_OK, name  # (no features: nothing to do)
+    finally:
+        nd.close()
+        est.close()
