@@ -112,7 +112,8 @@ typedef struct mld_params {
     int32_t radiusSearch_count_min;              /* :35  */
     int32_t do_use_histogram_segmentation;       /* :42  */
     int32_t histogram_segmentation_min_pointcount; /* :44 */
-    int32_t do_use_depth_segmentation;           /* :48  must be 0 (reference throws, DepthEstimator.cpp:608) */
+    int32_t do_use_depth_segmentation;           /* :48  must be 0 (reference throws, DepthEstimator.cpp:608); the mode
+                                                  *      itself, for a batch: mld_row_growth below */
     int32_t treshold_depth_enabled;              /* :78  */
     int32_t treshold_depth_mode;                 /* :79  0 Dispose, 1 Adjust */
     int32_t treshold_depth_max;                  /* :80  (int in the reference) */
@@ -1659,6 +1660,184 @@ int mld_nearest_depths_collect_tracks_device(mld_nearest_depths* nd, const float
                                              const int64_t* n_features, const int32_t* const* map, const int32_t* const* index,
                                              const int64_t* index_len, const double* const* cam, const int64_t* n_points,
                                              int list_capacity, mld_nearest_depth* const* record_out, int32_t* const* nb_out);
+
+/*
+ * Row-growth depths of a batch — the reference's second depth segmentation (do_use_depth_segmentation: 1, the value the
+ * shipped parameters.yaml:74 holds) for n_seq independent sequences: HelperLidarRowSegmentation cuts the visible list into
+ * lidar rows, grows a region along the row of the feature's nearest return and along one neighbouring row, and
+ * DepthEstimator::CalculateDepth (DepthEstimator.cpp:512-558) runs the triangle path on the grown points and answers
+ * MLD_SuccessRegionGrowing.  The reference keeps the mode behind a throw (:608) and mld_create keeps refusing it; this
+ * object is the mode as its code states it, quirks included, on the arrays mld_projected_clouds_export_device wrote.  It
+ * segments by 3-D continuity along the scan where the main path segments by a depth histogram.  All arithmetic is f64
+ * without contraction; every result is an integer or a float bit pattern.
+ *
+ * The rule.  Rows (HelperLidarRowSegmentation.cpp:18-46): walking the visible list in order with lastX = (double)INT_MIN,
+ *   visible point i opens a row iff x_i > lastX + 50 (strictly), then lastX = x_i; point 0 always opens row 0.  Rows are
+ *   contiguous ranges of the visible list: row r is [row_start[r], row_start[r + 1]).  The segmenter assumes that u falls
+ *   along a beam and jumps up at the next one, and checks nothing; a cloud scanned the other way is a few very long rows.
+ * The seed (DepthEstimator.cpp:509-530, :687-724): the neighbours of the narrow window in scan order (n_nb; (unsigned)n_nb <
+ *   radiusSearch_count_min: type 2).  CalculateNearestPoint folds with a FLOAT accumulator: m = +inf; z_i < (double)m: m =
+ *   (float)z_i, the seed is i - two returns closer than float resolution resolve either way.  No seed (every z NaN or
+ *   +inf): MLD_HistogramNoLocalMax at once.  z_seed > (double)treshold_depth_max: MLD_TresholdDepthGlobalGreaterMax at
+ *   once, whether or not treshold_depth_enabled is set.
+ * The second seed (HelperLidarRowSegmentation.cpp:68-157, :277-300), on the rows r - 1 and r + 1 of the seed's row r where
+ *   they exist: the first column c with x_c < fx && x_{c-1} >= fx (x_{-1} = INT_MIN: column 0 does not match); none: the
+ *   row has no point.  Else c if |p_c - f|^2 < |p_c - p_{c-1}|^2 - the second distance is between the two returns - else
+ *   c - 1.  Neither row: state -1.  Both: the top row first iff distTop < distBottom (2-D, to the feature; a tie puts the
+ *   bottom row first).  The first of them whose 3-D distance to the seed is <= maxDistSeedToSeed, else state -2.
+ * getMaxDist(thr, start, grad, z_seed) (:302-313): start where z_seed <= thr, else start + (z_seed - start) * grad - the
+ *   delta is taken from start, not from thr.
+ * Growth (:159-275, :359-368): the call sites hand (maxDistNeighborToSeed, maxDistNeighbor) to the parameters named
+ *   (maxDistanceNeighbor, maxDistanceSeed) - the roles are swapped.  Distances are sqrt((dx * dx + dy * dy) + dz * dz).  The
+ *   seed's row is grown with count / 2 (int division; -1 stays -1), then the second seed's row with count, onto the same
+ *   list; the seeds themselves are never in it.  count < 0: up the columns until the row ends, d(p, seed) >
+ *   maxDistanceSeed or d(p, last) > maxDistanceNeighbor, then down the columns by the same rule WITHOUT resetting `last`.
+ *   count >= 0: a two-pointer merge takes the side whose next point is closer to the seed ('<=' takes the upper side), no
+ *   neighbour test; it ends as soon as EITHER side runs out, the taken point is farther than maxDistanceSeed, or the list
+ *   holds count entries.  Nothing added by the second call: state -3, else state 1.
+ * The depth (DepthEstimator.cpp:551-556, :903-1036), state 1: CalculateDepthSegmented on the grown list in its order - the
+ *   max-spanning triangle or the first three points, the planarity check if configured, the viewing ray through the exact
+ *   (u, v), the thresholds on the list's min and max z; no count test, no histogram.  MLD_Success becomes
+ *   MLD_SuccessRegionGrowing.  Everything else - the states -1, -2, -3 and a failed triangle - decides nothing: the
+ *   ordinary path runs and its result stands (:564-572).  The whole mode is therefore: this stage's result where it decides
+ *   (type 20, the early 4, the early 3), the product's result everywhere else - which the in-place merge below writes.
+ *
+ * mld_row_growth_params: the eight depth_segmentation_* values with the reference's names and spelling;
+ *   mld_row_growth_params_default gives DepthEstimatorParameters.h:52-60, mld_row_growth_params_yaml the shipped
+ *   parameters.yaml:77-91.  depth_segmentation_max_pointcount is stored as a double there and truncated at the call.
+ *
+ * mld_row_growth_cloud, one per sequence, 16 bytes in DEVICE memory, written completely by every segment call:
+ *   n_rows        rows of the visible list: complete, also beyond row_capacity
+ *   n_vis         visible points segmented: min(n_visible, capacity[s])
+ *   longest_row   points of the longest row
+ *   flags         MLD_ROW_GROWTH_FLAG_ROWS_TRUNCATED: n_rows > row_capacity
+ * mld_row_growth, one per feature, 72 bytes; every record is written completely on every call:
+ *   type          MLD_SuccessRegionGrowing, the early MLD_TresholdDepthGlobalGreaterMax, the early MLD_HistogramNoLocalMax,
+ *                 MLD_RadiusSearchInsufficientPoints, or MLD_Unspecified: this stage decides nothing
+ *   state         calculateNeighborPoints' result 1, -1, -2, -3; 0 when not reached
+ *   grown_type    what CalculateDepthSegmented gave on the grown list; 0 when not reached
+ *   flags         MLD_ROW_GROWTH_FLAG_*
+ *   n_nb          neighbours in the narrow window
+ *   seed_vis, second_vis   visible indices of the two seeds, -1 without
+ *   seed_row, second_row   their rows, -1 without
+ *   n_first       list entries that came from the seed's row
+ *   n_grown       list entries in all: complete, also beyond MLD_ROW_GROWTH_MAX_LIST
+ *   corner_vis    visible indices of the triangle's corners, -1 without corners
+ *   depth         -1 unless type == MLD_SuccessRegionGrowing
+ *   seed_z        camera z of the seed, NaN without one
+ * Flags: BAD_INPUT - a map, index or row value points outside its array (map values as at mld_nearest_depths; a row whose
+ *   bounds leave [0, min(n_vis, index_len)] or run backwards is empty; a row point whose index lies outside the cloud ends
+ *   a loop as the row's end would; a seed that no row holds ends the feature with MLD_Unspecified, state 0); no read leaves
+ *   the arrays as the host tables size them.  NONFINITE_FEATURE - type 2.  ROWS_TRUNCATED - every feature of that sequence
+ *   gets MLD_Unspecified, state 0 and nothing else is looked at.  LIST_CAPPED - unbounded growth passed
+ *   MLD_ROW_GROWTH_MAX_LIST entries: n_grown is complete, the type is MLD_Unspecified, the tail is not run.
+ *
+ * mld_row_growth_create: an object bound to `ctx` (its stream, its device) for calls of n_seq (1 .. 65536) sequences of up
+ *   to max_features (1 .. 16 777 216) features and max_points (1 .. 8 388 607) visible points each, with row tables of
+ *   row_capacity (1 .. MLD_ROW_GROWTH_MAX_ROWS) rows.  params, growth and camera are copied; params->do_use_depth_segmentation
+ *   may hold either value.  All memory is allocated here, none per call:
+ *     device  n_seq * (8 * ceil(max_points / 64) + 16 * ceil(max_points / 1024) + 4 + 152) bytes   (break mask per 64 points,
+ *             break count and gaps per 1024 points; the descriptors of both calls)
+ *     pinned  16 * 152 * n_seq bytes   (the two descriptor rings)
+ *   The sizes are checked before the context is looked at (n_seq, max_features, max_points, row_capacity:
+ *   MLD_ERR_INVALID_ARG with a text naming the argument), then the context, then params, growth, camera and T_cam_lidar
+ *   (null), the count (-1, or 0 .. MLD_ROW_GROWTH_MAX_COUNT), and then, still without a use of the context, what
+ *   mld_nearest_depths_create refuses of a parameter set and a camera, with its codes and texts (do_use_PCA and
+ *   set_all_depths_to_zero first), a transform that is not finite, and a wide window of more than 1024 cells.  Returns NULL
+ *   on failure with the reason in *status_out (optional) and the text in mld_row_growth_last_error(NULL).  Destroy the
+ *   object before its context.
+ *
+ * mld_row_growth_segment_device, the cloud stage, once per cloud: HOST tables of n_seq entries, consumed before the call
+ *   returns; every array they name is DEVICE memory.
+ *   uv[s], capacity[s], n_visible_dev   as mld_projected_clouds_export_device wrote them: 2 x capacity[s] f64 and the int64
+ *                       array of n_seq counts.  capacity[s] <= max_points; uv[s] may be NULL where capacity[s] is 0.
+ *   row_start_out[s]    row_capacity + 1 int32.  Entries 0 .. min(n_rows, row_capacity) are written - row_start[n_rows] is
+ *                       n_vis where nothing was truncated - and nothing behind them is touched.
+ *   cloud_out_dev       n_seq records.
+ *   Asynchronous on the context's stream, three kernels behind the descriptor upload (k_rg_pass, k_rg_scan, k_rg_write: the
+ *   pass / scan / write compaction over the break flags), no atomics, no synchronisation, nothing comes back to the host.
+ *
+ * mld_row_growth_collect_device (uv[s] 2 x n_features[s] f64) and mld_row_growth_collect_tracks_device (u[s], v[s] f32,
+ *   truncated as at mld_nearest_depths_collect_tracks_device), the feature stage: HOST tables as at
+ *   mld_nearest_depths_collect_device, plus
+ *   vis_uv[s]           the uv array the segment call read, at least 2 x index_len[s] f64
+ *   row_start[s], cloud_dev   what the segment call wrote for these clouds; n_rows is read on the GPU
+ *   list_capacity       0 .. MLD_ROW_GROWTH_MAX_LIST
+ *   record_out[s]       n_features[s] records
+ *   grown_out           optional (the table, or single entries): list_capacity x n_features[s] int32, feature i's row at
+ *                       i * list_capacity: the visible indices of the grown list in its order.  The first min(n_grown,
+ *                       list_capacity, MLD_ROW_GROWTH_MAX_LIST) entries of a row are written, nothing behind them is touched.
+ *   depth_io, type_io   optional (the tables, or single entries): n_features[s] f64 (tracks form: f32) and int32, the
+ *                       outputs of mld_calculate_depths_device (the tracklet layer's) for these features.  Where the
+ *                       record decides (type 20, 4 or 3) depth and type are overwritten; everywhere else they are not
+ *                       touched.  With them the batch holds what CalculateDepth returns under do_use_depth_segmentation: 1.
+ *   Asynchronous on the context's stream, two launches: the descriptor upload and k_row_growth, ONE WAVEFRONT PER FEATURE.
+ *   MLD_ERR_INVALID_ARG with a text naming the function and the argument (mld_row_growth_last_error; "null object (rg)" of
+ *   NULL for a null object) on what mld_nearest_depths_collect_device refuses and on a null table vis_uv or row_start, a
+ *   null cloud_dev, a null vis_uv (index_len[s] > 0) or row_start array of a sequence with features, list_capacity out of
+ *   range, an array that is not naturally aligned.  MLD_ERR_CAPACITY as there.
+ */
+#define MLD_ROW_GROWTH_MAX_COUNT 256    /* depth_segmentation_max_pointcount */
+#define MLD_ROW_GROWTH_MAX_LIST 1024    /* entries of a grown list that are kept */
+#define MLD_ROW_GROWTH_MAX_ROWS 65536   /* row_capacity */
+enum { MLD_ROW_GROWTH_FLAG_BAD_INPUT = 1, MLD_ROW_GROWTH_FLAG_NONFINITE_FEATURE = 2, MLD_ROW_GROWTH_FLAG_ROWS_TRUNCATED = 4,
+       MLD_ROW_GROWTH_FLAG_LIST_CAPPED = 8 };
+
+typedef struct mld_row_growth_params {  /* 64 bytes */
+    double depth_segmentation_max_treshold_gradient;                        /* DepthEstimatorParameters.h:52 */
+    double depth_segmentation_max_neighbor_distance;                        /* :53 */
+    double depth_segmentation_max_neighbor_distance_gradient;               /* :54 */
+    double depth_segmentation_max_neighbor_to_seedpoint_distance;           /* :55 */
+    double depth_segmentation_max_seedpoint_to_seedpoint_distance_gradient; /* :56 */
+    double depth_segmentation_max_seedpoint_to_seedpoint_distance;          /* :57 */
+    double depth_segmentation_max_neighbor_to_seedpoint_distance_gradient;  /* :58 */
+    int32_t depth_segmentation_max_pointcount;                              /* :60  -1: unbounded */
+    int32_t pad_;
+} mld_row_growth_params;
+
+typedef struct mld_row_growth_cloud {   /* 16 bytes */
+    int32_t n_rows, n_vis, longest_row, flags;
+} mld_row_growth_cloud;
+
+typedef struct mld_row_growth {         /* 72 bytes, 8-byte aligned */
+    int32_t type;           /* 20, the early 4, the early 3, 2, or MLD_Unspecified */
+    int32_t state;          /* 1, -1, -2, -3; 0 when not reached */
+    int32_t grown_type;     /* CalculateDepthSegmented on the grown list; 0 when not reached */
+    int32_t flags;          /* MLD_ROW_GROWTH_FLAG_* */
+    int32_t n_nb;           /* neighbours in the narrow window */
+    int32_t seed_vis, second_vis;  /* visible indices of the seeds, -1 without */
+    int32_t seed_row, second_row;  /* their rows, -1 without */
+    int32_t n_first, n_grown;      /* list entries from the seed's row; in all */
+    int32_t corner_vis[3];  /* visible indices of the corners, -1 without corners */
+    double  depth;          /* -1 unless type == MLD_SuccessRegionGrowing */
+    double  seed_z;         /* camera z of the seed, NaN without one */
+} mld_row_growth;
+
+void mld_row_growth_params_default(mld_row_growth_params* g);
+void mld_row_growth_params_yaml(mld_row_growth_params* g);
+
+typedef struct mld_row_growth_unit mld_row_growth_unit;
+mld_row_growth_unit* mld_row_growth_create(mld_ctx* ctx, int n_seq, int64_t max_features, int64_t max_points, int row_capacity,
+                                           const mld_params* params, const mld_row_growth_params* growth,
+                                           const mld_camera* camera, const double T_cam_lidar[12], int* status_out);
+void mld_row_growth_destroy(mld_row_growth_unit* rg);
+const char* mld_row_growth_last_error(const mld_row_growth_unit* rg);
+int mld_row_growth_segment_device(mld_row_growth_unit* rg, const double* const* uv, const int64_t* capacity,
+                                  const int64_t* n_visible_dev, int32_t* const* row_start_out,
+                                  mld_row_growth_cloud* cloud_out_dev);
+int mld_row_growth_collect_device(mld_row_growth_unit* rg, const double* const* uv, const int64_t* n_features,
+                                  const int32_t* const* map, const int32_t* const* index, const int64_t* index_len,
+                                  const double* const* cam, const int64_t* n_points, const double* const* vis_uv,
+                                  const int32_t* const* row_start, const mld_row_growth_cloud* cloud_dev, int list_capacity,
+                                  mld_row_growth* const* record_out, int32_t* const* grown_out, double* const* depth_io,
+                                  int32_t* const* type_io);
+int mld_row_growth_collect_tracks_device(mld_row_growth_unit* rg, const float* const* u, const float* const* v,
+                                         const int64_t* n_features, const int32_t* const* map, const int32_t* const* index,
+                                         const int64_t* index_len, const double* const* cam, const int64_t* n_points,
+                                         const double* const* vis_uv, const int32_t* const* row_start,
+                                         const mld_row_growth_cloud* cloud_dev, int list_capacity,
+                                         mld_row_growth* const* record_out, int32_t* const* grown_out, float* const* depth_io,
+                                         int32_t* const* type_io);
 
 /*
  * Merged sweeps of a batch — the last few lidar sweeps of n_seq independent sequences carried into the current lidar

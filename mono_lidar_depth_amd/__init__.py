@@ -9,7 +9,7 @@ from .depth_estimator import (NO_PLANE, CameraPinhole, DepthEstimator, DepthEsti
                               GroundPlane, RansacPlane, SemanticPlane)
 
 from .track_archive import ArchivedTrack, TrackArchive
-from .tracklets import (CoverageMaps, DepthImages, DepthReports, FeatureTraces, NearestDepths, PlaneInliers, ProjectedClouds, RansacPlanes, RegionDepths, SemanticLabels, SemanticPlanes, SweepMerge, TrackletBatch, TrackletDepthModule, TrackletStore)
+from .tracklets import (CoverageMaps, DepthImages, DepthReports, FeatureTraces, NearestDepths, PlaneInliers, ProjectedClouds, RansacPlanes, RegionDepths, RowGrowth, SemanticLabels, SemanticPlanes, SweepMerge, TrackletBatch, TrackletDepthModule, TrackletStore)
 
-__all__ = ["TrackletDepthModule", "TrackletBatch", "TrackletStore", "TrackArchive", "ArchivedTrack", "SemanticLabels", "SemanticPlanes", "RansacPlanes", "ProjectedClouds", "DepthReports", "PlaneInliers", "FeatureTraces", "CoverageMaps", "DepthImages", "RegionDepths", "NearestDepths", "SweepMerge", "MldCamera", "MldParams", "params_c0", "params_default", "params_from_file", "RESULT_TYPE_NAMES",
+__all__ = ["TrackletDepthModule", "TrackletBatch", "TrackletStore", "TrackArchive", "ArchivedTrack", "SemanticLabels", "SemanticPlanes", "RansacPlanes", "ProjectedClouds", "DepthReports", "PlaneInliers", "FeatureTraces", "CoverageMaps", "DepthImages", "RegionDepths", "NearestDepths", "SweepMerge", "RowGrowth", "MldCamera", "MldParams", "params_c0", "params_default", "params_from_file", "RESULT_TYPE_NAMES",
            "NO_PLANE", "RansacPlane", "SemanticPlane", "CameraPinhole", "DepthEstimator", "DepthEstimatorError", "ExceptionPclInvalid", "GroundPlane"]

@@ -216,6 +216,46 @@ class MldNearestDepth(C.Structure):
                 ("depth", C.c_double), ("nearest_z", C.c_double), ("corner_vis", C.c_int32 * 3), ("pad_", C.c_int32)]
 
 
+# mld_row_growth: the bits of mld_row_growth::flags (the third also of mld_row_growth_cloud::flags) and the limits of the
+# count, the kept list and the row capacity (include/mld.h)
+(MLD_ROW_GROWTH_FLAG_BAD_INPUT, MLD_ROW_GROWTH_FLAG_NONFINITE_FEATURE, MLD_ROW_GROWTH_FLAG_ROWS_TRUNCATED,
+ MLD_ROW_GROWTH_FLAG_LIST_CAPPED) = 1, 2, 4, 8
+MLD_ROW_GROWTH_MAX_COUNT, MLD_ROW_GROWTH_MAX_LIST, MLD_ROW_GROWTH_MAX_ROWS = 256, 1024, 65536
+
+
+class MldRowGrowthParams(C.Structure):
+    """mld_row_growth_params (include/mld.h): the depth_segmentation_* values of DepthEstimatorParameters.h:52-60, 64 bytes."""
+    _fields_ = [("depth_segmentation_max_treshold_gradient", C.c_double),
+                ("depth_segmentation_max_neighbor_distance", C.c_double),
+                ("depth_segmentation_max_neighbor_distance_gradient", C.c_double),
+                ("depth_segmentation_max_neighbor_to_seedpoint_distance", C.c_double),
+                ("depth_segmentation_max_seedpoint_to_seedpoint_distance_gradient", C.c_double),
+                ("depth_segmentation_max_seedpoint_to_seedpoint_distance", C.c_double),
+                ("depth_segmentation_max_neighbor_to_seedpoint_distance_gradient", C.c_double),
+                ("depth_segmentation_max_pointcount", C.c_int32), ("pad_", C.c_int32)]
+
+    def replace(self, **kw) -> "MldRowGrowthParams":
+        out = MldRowGrowthParams.from_buffer_copy(self)
+        for k, v in kw.items():
+            if not hasattr(out, k):
+                raise AttributeError(k)
+            setattr(out, k, v)
+        return out
+
+
+class MldRowGrowthCloud(C.Structure):
+    """mld_row_growth_cloud (include/mld.h): one sequence of mld_row_growth_segment_device, 16 bytes."""
+    _fields_ = [("n_rows", C.c_int32), ("n_vis", C.c_int32), ("longest_row", C.c_int32), ("flags", C.c_int32)]
+
+
+class MldRowGrowth(C.Structure):
+    """mld_row_growth (include/mld.h): one feature of mld_row_growth_collect_*_device, 72 bytes = 9 int64."""
+    _fields_ = [("type", C.c_int32), ("state", C.c_int32), ("grown_type", C.c_int32), ("flags", C.c_int32),
+                ("n_nb", C.c_int32), ("seed_vis", C.c_int32), ("second_vis", C.c_int32), ("seed_row", C.c_int32),
+                ("second_row", C.c_int32), ("n_first", C.c_int32), ("n_grown", C.c_int32), ("corner_vis", C.c_int32 * 3),
+                ("depth", C.c_double), ("seed_z", C.c_double)]
+
+
 # mld_sweep_merge: the bit of mld_sweep_merge_record::flags and the limit of max_sweeps (include/mld.h)
 MLD_SWEEP_FLAG_TRUNCATED = 1
 MLD_SWEEP_MAX_SWEEPS = 16
@@ -377,6 +417,19 @@ _SIGNATURES = [
      [_P(C.c_int64), _P(C.c_void_p), _P(C.c_int64), C.c_int] + [_P(C.c_void_p)] * 2),
     ("mld_nearest_depths_collect_tracks_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 2 + [_P(C.c_int64)] +
      [_P(C.c_void_p)] * 2 + [_P(C.c_int64), _P(C.c_void_p), _P(C.c_int64), C.c_int] + [_P(C.c_void_p)] * 2),
+    ("mld_row_growth_params_default", None, [_P(MldRowGrowthParams)]),
+    ("mld_row_growth_params_yaml", None, [_P(MldRowGrowthParams)]),
+    ("mld_row_growth_create", C.c_void_p, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, _P(MldParams),
+                                           _P(MldRowGrowthParams), _P(MldCamera), _P(C.c_double), _P(C.c_int)]),
+    ("mld_row_growth_destroy", None, [C.c_void_p]),
+    ("mld_row_growth_last_error", C.c_char_p, [C.c_void_p]),
+    ("mld_row_growth_segment_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64), C.c_void_p, _P(C.c_void_p),
+                                                C.c_void_p]),
+    ("mld_row_growth_collect_device", C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)] + [_P(C.c_void_p)] * 2 +
+     [_P(C.c_int64), _P(C.c_void_p), _P(C.c_int64)] + [_P(C.c_void_p)] * 2 + [C.c_void_p, C.c_int] + [_P(C.c_void_p)] * 4),
+    ("mld_row_growth_collect_tracks_device", C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 2 + [_P(C.c_int64)] +
+     [_P(C.c_void_p)] * 2 + [_P(C.c_int64), _P(C.c_void_p), _P(C.c_int64)] + [_P(C.c_void_p)] * 2 + [C.c_void_p, C.c_int] +
+     [_P(C.c_void_p)] * 4),
     ("mld_sweep_merge_create", C.c_void_p, [C.c_void_p, C.c_int, C.c_int, C.c_int64, _P(C.c_int)]),
     ("mld_sweep_merge_destroy", None, [C.c_void_p]),
     ("mld_sweep_merge_last_error", C.c_char_p, [C.c_void_p]),
@@ -452,6 +505,20 @@ def params_default() -> MldParams:
     p = MldParams()
     load().mld_params_default(C.byref(p))
     return p
+
+
+def row_growth_params_default() -> MldRowGrowthParams:
+    """The depth_segmentation_* defaults of DepthEstimatorParameters.h:52-60."""
+    g = MldRowGrowthParams()
+    load().mld_row_growth_params_default(C.byref(g))
+    return g
+
+
+def row_growth_params_yaml() -> MldRowGrowthParams:
+    """The depth_segmentation_* values of the shipped parameters.yaml:77-91."""
+    g = MldRowGrowthParams()
+    load().mld_row_growth_params_yaml(C.byref(g))
+    return g
 
 
 def params_from_file(path: str) -> MldParams:

@@ -236,7 +236,7 @@ def _result_tensor(t, shape, size, name):
 
 class _BatchObject:
     """What TrackletStore, SemanticLabels, SemanticPlanes, RansacPlanes, ProjectedClouds, DepthReports, PlaneInliers,
-    FeatureTraces, CoverageMaps, DepthImages, RegionDepths, NearestDepths and SweepMerge share: an object of the C-ABI (mld_<_NAME>_create / _destroy /
+    FeatureTraces, CoverageMaps, DepthImages, RegionDepths, NearestDepths, SweepMerge and RowGrowth share: an object of the C-ABI (mld_<_NAME>_create / _destroy /
     _last_error) on an estimator's context, its handle in the attribute named _HANDLE, the tensors of the calls that may
     still be queued, and one copy of every argument check.  The helpers, here and above:
 
@@ -780,7 +780,7 @@ class PlaneInliers(_BatchObject):
 
 
 class _FeatureUnit(_BatchObject):
-    """What FeatureTraces and NearestDepths share - one record per feature, on the tensors ProjectedClouds.export wrote:
+    """What FeatureTraces, NearestDepths and RowGrowth share - one record per feature, on the tensors ProjectedClouds.export wrote:
     the feature tables of both forms with their refusals, what the exported cloud of a sequence with features must hold,
     the leading arguments of the C calls, and records().  WORDS: int64 words of a record, DTYPE: its fields."""
 
@@ -1114,6 +1114,98 @@ class NearestDepths(_FeatureUnit):
         self._collect(self._track_counts(u, v), (u, v), pixel_map, index, cam, record, list_capacity, nb)
 
 
+class RowGrowth(_FeatureUnit):
+    """The reference's second depth segmentation - region growing along lidar rows, do_use_depth_segmentation: 1 - for S
+    sequences per call (mld_row_growth_*, include/mld.h): segment() cuts the visible list of every cloud into rows (once
+    per cloud), collect() / collect_tracks() find per feature the nearest return of its search window, a second seed in a
+    neighbouring row, grow both rows and run the triangle path on the grown points (type 20, SuccessRegionGrowing).  The
+    record says what the stage decided (type 20, the early 4 and 3) or that it decided nothing (type 0); with depth and
+    types given, the decided entries are merged into the product's outputs in place, which then hold what CalculateDepth
+    returns in that mode.  It runs on the tensors ProjectedClouds.export wrote (uv, n_visible, pixel_map, index, cam).
+    `growth` (default: capi.row_growth_params_default(), the header values; capi.row_growth_params_yaml(): the shipped
+    file's) and `parameters` (default: the estimator's) are copied at creation; do_use_PCA and set_all_depths_to_zero are
+    refused.  Lists of S torch CUDA tensors in and out; asynchronous on the estimator's stream.  Close it before its
+    estimator."""
+
+    _NAME, _HANDLE = "row_growth", "_rg"
+    WORDS = 9  # int64 words of a record (capi.MldRowGrowth, 72 bytes)
+    DTYPE = np.dtype(capi.MldRowGrowth)
+    CLOUD_DTYPE = np.dtype(capi.MldRowGrowthCloud)
+    MAX_COUNT, MAX_LIST, MAX_ROWS = capi.MLD_ROW_GROWTH_MAX_COUNT, capi.MLD_ROW_GROWTH_MAX_LIST, capi.MLD_ROW_GROWTH_MAX_ROWS
+
+    def __init__(self, estimator: DepthEstimator, n_seq: int, max_features: int, max_points: int, row_capacity: int,
+                 growth=None, parameters=None):
+        self.S, self.max_features, self.max_points = int(n_seq), int(max_features), int(max_points)
+        self.row_capacity = int(row_capacity)
+        self.growth = growth if growth is not None else capi.row_growth_params_default()
+        par, cam, T = self._calibration(estimator, "parameters", "camera", "transform", parameters=parameters)
+        self._create(estimator, self.S, self.max_features, self.max_points, self.row_capacity, par, C.byref(self.growth), cam, T)
+
+    @classmethod
+    def cloud_records(cls, cloud) -> np.ndarray:
+        """The tensor segment() wrote (int32 [S, 4]) as a NumPy record array with the fields of CLOUD_DTYPE (copies to
+        the host, which synchronises as usual)."""
+        return np.ascontiguousarray(cloud.cpu().numpy()).reshape(-1).view(cls.CLOUD_DTYPE)
+
+    def segment(self, uv, n_visible, row_start, cloud):
+        """The cloud stage, once per cloud.  uv: S float64 CUDA tensors [capacity, 2] and n_visible: the int64 CUDA tensor
+        [S], both as ProjectedClouds.export wrote them (an entry of uv None: a sequence without capacity); row_start: S
+        int32 CUDA tensors of at least row_capacity + 1 entries; cloud: an int32 CUDA tensor [S, 4]
+        (capi.MldRowGrowthCloud, see cloud_records())."""
+        self._lengths(uv=uv, row_start=row_start)
+        _result_tensor(n_visible, (self.S,), 8, "n_visible")
+        _result_tensor(cloud, (self.S, 4), 4, "cloud")
+        caps = []
+        for s in range(self.S):
+            _holds(uv[s], s, 0, 8, "uv")
+            _holds(row_start[s], s, self.row_capacity + 1, 4, "row_start", required=True)
+            caps.append(_entries(uv[s], 2))
+        self._check(self._lib.mld_row_growth_segment_device(self._rg, self._ptrs(uv), self._i64(caps), int(n_visible.data_ptr()),
+                                                            self._ptrs(row_start), int(cloud.data_ptr())))
+        self._hold(uv, n_visible, row_start, cloud, call="segment")
+
+    def _collect(self, ns, feats, maps, index, cam, vis_uv, row_start, cloud, record, list_capacity, grown, depth, types):
+        cap = int(list_capacity)
+        self._lengths(pixel_map=maps, index=index, cam=cam, vis_uv=vis_uv, row_start=row_start, record=record, grown=grown,
+                      depth=depth, types=types)
+        if not 0 <= cap <= self.MAX_LIST:
+            raise ValueError(f"list_capacity must be in 0 .. {self.MAX_LIST}")
+        _result_tensor(cloud, (self.S, 4), 4, "cloud")
+        self._cloud_holds(ns, maps, index, cam, "record", record, cap, {"grown": grown})
+        tracks = len(feats) == 2
+        for s, n in enumerate(ns):
+            if n == 0:
+                continue
+            _holds(vis_uv[s], s, 2 * _entries(index[s]), 8, "vis_uv", required=True)
+            _holds(row_start[s], s, self.row_capacity + 1, 4, "row_start", required=True)
+            _holds(_at(depth, s), s, n, 4 if tracks else 8, "depth")
+            _holds(_at(types, s), s, n, 4, "types")
+        fn = self._lib.mld_row_growth_collect_tracks_device if tracks else self._lib.mld_row_growth_collect_device
+        self._check(fn(self._rg, *self._cloud_args(ns, feats, maps, index, cam), self._ptrs(vis_uv), self._ptrs(row_start),
+                       int(cloud.data_ptr()), cap, self._ptrs(record), self._opt(grown), self._opt(depth), self._opt(types)))
+        self._hold(*feats, maps, index, cam, vis_uv, row_start, cloud, record, grown, depth, types)
+
+    def collect(self, uv, pixel_map, index, cam, vis_uv, row_start, cloud, record, list_capacity: int = 0, grown=None,
+                depth=None, types=None):
+        """uv: S contiguous float64 CUDA tensors [n, 2] (an entry None: a sequence without features); pixel_map, index,
+        cam: as NearestDepths.collect takes them; vis_uv, row_start, cloud: what segment() read and wrote for these
+        clouds; record: S int64 CUDA tensors of at least 9 * n entries (a contiguous [n, 9]: capi.MldRowGrowth, see
+        records()); grown: None, or S int32 CUDA tensors of at least list_capacity * n entries (a contiguous [n,
+        list_capacity]; single entries may be None): the visible indices of the grown list in its order, the first
+        min(n_grown, list_capacity) of them; depth, types: None, or S float64 / int32 CUDA tensors [n] (single entries
+        may be None), the outputs of the depth call for these features: overwritten where the record decides, untouched
+        elsewhere."""
+        self._collect(self._uv_counts(uv), (uv,), pixel_map, index, cam, vis_uv, row_start, cloud, record, list_capacity, grown,
+                      depth, types)
+
+    def collect_tracks(self, u, v, pixel_map, index, cam, vis_uv, row_start, cloud, record, list_capacity: int = 0, grown=None,
+                       depth=None, types=None):
+        """As collect(), on the tensors of TrackletBatch.prepare_step() / prepare(): u, v (u_new, v_new): S float32 CUDA
+        tensors [n]; depth: float32 [n] (d_cur)."""
+        self._collect(self._track_counts(u, v), (u, v), pixel_map, index, cam, vis_uv, row_start, cloud, record, list_capacity,
+                      grown, depth, types)
+
+
 class SweepMerge(_BatchObject):
     """The last few lidar sweeps of S sequences carried into the current lidar frame and concatenated, current sweep first
     (mld_sweep_merge_*, include/mld.h - the transform's operation order and the two drop tests are stated there): every
@@ -1212,7 +1304,8 @@ class TrackletBatch:
                    "depth_image_maps": (DepthImages, "attach_depth_images", ()),
                    "region_depth_boxes": (RegionDepths, "attach_region_depths", ()),
                    "nearest_depth_lists": (NearestDepths, "attach_nearest_depths", ("max_tracks",)),
-                   "sweep_merger": (SweepMerge, "attach_sweep_merge", ())}
+                   "sweep_merger": (SweepMerge, "attach_sweep_merge", ()),
+                   "row_growth_lists": (RowGrowth, "attach_row_growth", ("max_tracks",))}
 
     def __init__(self, parameters, camera: CameraPinhole, transform_lidar_to_cam, n_seq: int, max_tracks: int,
                  device: int = 0, list_capacity=None):
@@ -1605,6 +1698,39 @@ class TrackletBatch:
         out = {"record": [torch.empty((n, NearestDepths.WORDS), dtype=torch.int64, device=dev) for n in ns],
                "nb": [torch.empty((n, cap), dtype=torch.int32, device=dev) for n in ns] if cap else None}
         nd.collect_tracks(u_new, v_new, clouds["pixel_map"], clouds["index"], clouds["cam"], out["record"], cap, out["nb"])
+        self.est.orderTorchAfter()
+        return out
+
+    def attach_row_growth(self, growth=None, row_capacity: int = 4096, max_points: int = 1 << 19) -> RowGrowth:
+        """The region growing along lidar rows of the S sequences that row_growth() runs, for up to max_tracks tracks per
+        sequence, clouds of up to max_points visible points and row_capacity (1 .. RowGrowth.MAX_ROWS) rows each.  growth:
+        a capi.MldRowGrowthParams (None: capi.row_growth_params_default()).  It takes the estimator's parameters as they
+        are now."""
+        return self._attach("row_growth_lists", max_points, row_capacity, growth)
+
+    def row_growth(self, f, clouds, list_capacity: int = 0, merge=None):
+        """A depth for the tracks of table `f` (prepare_step() / prepare()) from the reference's region growing on this
+        frame's clouds: RowGrowth.segment on `clouds`, the dict projected_clouds(cam=True, pixel_map=True) returned for
+        the same clouds with a capacity that did not truncate, then RowGrowth.collect_tracks on the table's u_new, v_new.
+        merge: None, or the pair (depth, types) of S float32 / int32 tensors [n] the step wrote for these tracks
+        (f["current"]): the entries the stage decides (type 20, 4, 3) are overwritten in place, the others not touched.
+        Returns a dict with record (S int64 [n, 9]: capi.MldRowGrowth, see RowGrowth.records()), grown (S int32 [n,
+        list_capacity]: a row holds the first min(n_grown, list_capacity) visible indices of its list, the rest is not
+        written; None with list_capacity 0), row_start (S int32 [row_capacity + 1]) and cloud (int32 [S, 4]:
+        capi.MldRowGrowthCloud, see RowGrowth.cloud_records()).  No synchronisation: torch's current stream is made to
+        wait for the calls; a host read synchronises as usual.  attach_row_growth() first."""
+        import torch
+        rg = self._attached("row_growth_lists", "row_growth")
+        u_new, v_new, dev, ns = self._feature_tables(f, clouds)
+        cap = int(list_capacity)
+        depth, types = merge if merge is not None else (None, None)
+        out = {"record": [torch.empty((n, RowGrowth.WORDS), dtype=torch.int64, device=dev) for n in ns],
+               "grown": [torch.empty((n, cap), dtype=torch.int32, device=dev) for n in ns] if cap else None,
+               "row_start": [torch.empty(rg.row_capacity + 1, dtype=torch.int32, device=dev) for _ in ns],
+               "cloud": torch.empty((self.S, 4), dtype=torch.int32, device=dev)}
+        rg.segment(clouds["uv"], clouds["n_visible"], out["row_start"], out["cloud"])
+        rg.collect_tracks(u_new, v_new, clouds["pixel_map"], clouds["index"], clouds["cam"], clouds["uv"], out["row_start"],
+                          out["cloud"], out["record"], cap, out["grown"], depth, types)
         self.est.orderTorchAfter()
         return out
 
