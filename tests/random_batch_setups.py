@@ -1,5 +1,5 @@
-"""Random configurations for the batch units (depth images, feature traces, coverage maps, nearest depths): the parameter
-set, camera, mounting and scanner of test_randomized_gpu._random_setup(seed), with the camera scaled down so that the
+"""Random configurations for the batch units (depth images, feature traces, coverage maps, nearest depths, row growth): the
+parameter set, camera, mounting and scanner of test_randomized_gpu._random_setup(seed), with the camera scaled down so that the
 oracle can answer at EVERY pixel in well under a second and the windows hold enough returns to overflow a lane's 32-entry
 list, and the parameters changed only where the unit's refuse_config says so.  No GPU is used here."""
 import functools
@@ -12,10 +12,11 @@ from test_randomized_gpu import _random_setup
 
 # Fixed numbers: what they reach together is asserted in test_batch_units_randomized_cpu.py.
 SEEDS = tuple(range(12))
-UNITS = ("images", "traces", "coverage", "nearest")
+UNITS = ("images", "traces", "coverage", "nearest", "rows")
 # What a unit's refuse_config refuses of what _random_setup can draw.
 ADAPT = {"images": dict(do_use_PCA=0, plane_estimator_use_triangle_maximation=0, plane_estimator_use_mestimator=1),
-         "traces": dict(do_use_PCA=0), "coverage": dict(do_use_PCA=0), "nearest": dict(do_use_PCA=0)}
+         "traces": dict(do_use_PCA=0), "coverage": dict(do_use_PCA=0), "nearest": dict(do_use_PCA=0),
+         "rows": dict(do_use_PCA=0, set_all_depths_to_zero=0)}
 
 
 def wide_window(P, W, H):

@@ -85,7 +85,8 @@ def covered(seed, fr=None, plane=None, key=None):
 @pytest.mark.parametrize("seed", SEEDS)
 def test_the_setups_differ_from_the_generator_only_where_a_unit_refuses(seed):
     """Camera scaled by 1/4 (1/8 beyond 1242 columns), do_use_PCA off, for the depth images the M-estimator road fit; the
-    windows within what the units accept; traces, coverage maps and nearest depths on one parameter set."""
+    windows within what the units accept; traces, coverage maps, nearest depths and row growth on one parameter set (the
+    generator never draws set_all_depths_to_zero, which the row growth refuses as well)."""
     P0, cam0, T0, _, kw = _random_setup(seed)
     k = 8 if cam0.width > 1242 else 4
     seen = {}
@@ -99,13 +100,13 @@ def test_the_setups_differ_from_the_generator_only_where_a_unit_refuses(seed):
         changed = {n for n in kw if getattr(P, n) != getattr(P0, n)}
         assert changed <= {"do_use_PCA", "plane_estimator_use_triangle_maximation", "plane_estimator_use_mestimator"}
         assert unit == "images" or changed <= {"do_use_PCA"}
-        assert not P.do_use_PCA
+        assert not P.do_use_PCA and not P.set_all_depths_to_zero and not P0.set_all_depths_to_zero
         if unit == "images":
             assert not P.plane_estimator_use_triangle_maximation and P.plane_estimator_use_mestimator
         nx, ny = wide_window(P, cam.width, cam.height)
         assert nx <= 30 and ny <= 23  # (the generator's search areas are at most 14 x 14)
         assert nx <= 64 and ny <= 64 and nx * ny <= 1024
-    assert seen["traces"] == seen["coverage"] == seen["nearest"]
+    assert seen["traces"] == seen["coverage"] == seen["nearest"] == seen["rows"]
 
 
 @pytest.mark.parametrize("seed", SEEDS)
